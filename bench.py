@@ -7,8 +7,10 @@ A "step" is one pass of the hot path (loop body of the reference's main.py:142-1
 forwards + one backward + Nadam, G-step with G forward + D forward + backward + Nadam) over one synthetic
 batch; workload = BASELINE.json configs[1]: 64x64 RGB, batch 64 per GPU.  Weak scaling: per-GPU batch fixed,
 gradients averaged with RCCL all-reduce.  Inputs are resident in HBM before the timed region.
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel, timed live with HIP events on the launch
-stream) and, at N=1, `cpu_baseline` (the CPU oracle timed on this host)."""
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints that line, nothing more;
+`--full` adds the figures that take work of their own: `roofline` (dominant kernel, timed live with HIP events on the
+launch stream), `hbm_bound`, at N=1 `cpu_baseline` (the CPU oracle timed on this host) and, data-parallel, `data_parallel`
+(the exchange timed over extra steps).  `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy."""
 import argparse
 import json
 import os
@@ -34,14 +36,21 @@ def parse():
                          "slice, fp32 accumulation and storage (BASELINE configs[1] as named; tolerances in tests/test_gpu_bf16.py).  "
                          "fp8: operands as e4m3 on the fp8 matrix instruction (BASELINE configs[4]'s arithmetic; tests/test_gpu_fp8.py)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of a captured hipGraph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline / hbm_bound / cpu_baseline blocks and, "
+                         "data-parallel, the data_parallel block (off: the run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): the step's output "
+                         "record and both networks' parameters after its update; arrays above 2^20 elements as a fixed, seeded "
+                         "sample of 2^20 of them")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline block")
     ap.add_argument("--step-only", action="store_true",
-                    help="profiling runs: time the step only - no roofline / hbm_bound / cpu_baseline blocks (their launches would "
-                         "mix into a rocprofv3 trace of the step)")
+                    help="with --full: no roofline / hbm_bound / cpu_baseline blocks (what a plain run leaves out anyway; their "
+                         "launches would mix into a rocprofv3 trace of the step)")
     ap.add_argument("--concurrent-d", action="store_true",
                     help="run the three discriminator passes of the D-step on three streams (measured: no gain under "
                          "hipGraph replay on ROCm 7.0 - parallel branches are replayed almost serially)")
-    ap.add_argument("--cpu-steps", type=int, default=2)
+    ap.add_argument("--cpu-steps", type=int, default=2, help="with --full: timed steps of the cpu_baseline block")
     ap.add_argument("--wgrad-overlap", choices=("auto", "on", "off"), default="auto",
                     help="weight gradients on a second stream beside the backward pass's chain of input gradients (same values; the "
                          "data-parallel reducer picks such gradients up at the end of the pass - tests/test_gpu_dp.py).  auto = off: "
@@ -273,6 +282,27 @@ def cpu_baseline(cfg, batch, steps):
             "s_per_step": round(dt, 3)}
 
 
+DUMP_MAX_ELEMENTS = 1 << 20       # 4 MB per file; the step's seven outputs and two parameter sets stay under 64 MB at any size
+
+
+def dump_outputs(out, nets, path):
+    """What a caller of the timed path receives from its last step: every tensor of the step's output record, and each
+    network's parameters after that step's optimizer update (named_parameters() order, flattened and concatenated).  An array
+    with more than DUMP_MAX_ELEMENTS elements is written as the elements at a fixed set of positions, drawn without
+    replacement with a seed of its own and sorted, so that two runs of the same arguments write the same positions."""
+    import zlib
+    import numpy as np
+    arrays = {k: v.detach().reshape(-1) for k, v in out.items() if torch.is_tensor(v)}
+    arrays.update({name + "_parameters": torch.cat([p.detach().reshape(-1) for p in net.parameters()]) for name, net in nets.items()})
+    os.makedirs(path, exist_ok=True)
+    for name, flat in sorted(arrays.items()):
+        shape = tuple(out[name].shape) if name in out else (flat.numel(),)
+        if flat.numel() > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.numel(), DUMP_MAX_ELEMENTS, replace=False))
+            flat, shape = flat[torch.from_numpy(idx).to(flat.device)], (DUMP_MAX_ELEMENTS,)
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy().reshape(shape))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -358,8 +388,12 @@ def main():
         out = one_step()
     barrier()
     elapsed = time.perf_counter() - t0
+    d_error = float(out["d_error"])
+    g_error = float(out["g_error"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, {"G": G, "D": D}, args.dump_outputs)
     comm = None
-    if dp:
+    if dp and args.full:
         # a few extra steps with HIP events around the exchange: how much of it hides behind backward work
         red_g.timing = red_d.timing = True
         for _ in range(5):
@@ -391,8 +425,6 @@ def main():
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         assert torch.equal(lo, hi), "replicas diverged: parameter checksums %s vs %s" % (lo.tolist(), hi.tolist())
-    d_error = float(out["d_error"])
-    g_error = float(out["g_error"])
     assert d_error == d_error and g_error == g_error, "non-finite loss in the benchmark"
 
     if rank == 0:
@@ -421,7 +453,7 @@ def main():
         }
         if comm is not None:
             line["data_parallel"] = comm
-        if not args.step_only:
+        if args.full and not args.step_only:
             line["roofline"] = conv_roofline(cfg, B, dev, bf16=args.dtype == "bf16", fp8=args.dtype == "fp8")
             if S == 64:
                 line["hbm_bound"] = hbm_bound_block(B, dev)
@@ -432,7 +464,7 @@ def main():
             line["step_level"] = {"algorithmic_tflops": round(7.5e9 * B / step_s / 1e12, 2),
                                   "reference_graph_GBps": round(356e6 * B / step_s / 1e9, 1),
                                   "frac_of_hbm_peak": round(356e6 * B / step_s / 8.0e12, 4)}
-        if world == 1 and not args.no_cpu_baseline and not args.step_only:
+        if args.full and world == 1 and not args.no_cpu_baseline and not args.step_only:
             line["cpu_baseline"] = cpu_baseline(cfg, B, args.cpu_steps)
         print(json.dumps(line), flush=True)
     if dp:

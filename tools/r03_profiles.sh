@@ -5,8 +5,8 @@
 set -o pipefail
 O=gpurun_out/r03; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-python bench.py --steps 30 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
-python bench.py --steps 30 --warmup 5 --dtype bf16 --no-cpu-baseline > $O/bench_bf16.json 2> $O/bench_bf16.err || exit 1
+python bench.py --full --steps 30 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err || exit 1
+python bench.py --full --steps 30 --warmup 5 --dtype bf16 --no-cpu-baseline > $O/bench_bf16.json 2> $O/bench_bf16.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 10 --warmup 2 --step-only > $O/trace.log 2>&1 || exit 1
 python tools/prof_summary.py $O/trace 14 > $O/by_category.txt
 python tools/trace_by_grid.py $O/trace 14 "" 60 > $O/by_kernel_and_grid.txt
