@@ -339,6 +339,28 @@ int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, 
                   float* g_true, float* g_fake, float* g_aug, void* stream);
 int locate_g_loss(const float* d_fake, int B, float* loss, float* g_fake, void* stream);
 
+/* ---- device-side input pipeline (libs/utils.py:88-113: the reference's two ImageFolder transform chains, which it runs on the
+ *      CPU with torchvision / PIL).  `store`: uint8 [N, H, W, 3] device memory, 16-byte aligned - the data set after the
+ *      deterministic decode + Resize(2 S).  One call makes n samples: sample i reads image idx[i] and applies record i of `params`
+ *      (locate_input_param_record_bytes() = 32 bytes: int32 flip; int32 order - four 4-bit op codes, first op in the low bits,
+ *      0 brightness, 1 contrast, 2 saturation, anything else no-op (hue is off in the reference), so 0x3333 is the plain chain;
+ *      float brightness, contrast, saturation factors; int32 top, left, side of the square crop of the flipped image), then
+ *      resizes the crop to S x S and writes (u8 / 255 - 0.5) / 0.5 as fp32 [3, S, S]: samples [0, n_first) into out_first, the
+ *      others into out_rest (the plain and the augmented batch of one step in one launch).  The arithmetic is Pillow's, bit for
+ *      bit: Image.blend in fp32 per jitter op with uint8 between the ops, the contrast mean over the whole source image, the
+ *      antialiased BILINEAR resize in 22-bit fixed point, horizontal pass first.
+ *      `coef`: int32 [side_hi - side_lo + 1][S][2 + ktaps] = {first tap, tap count, weights * 2^22} per crop side and output
+ *      index (one table serves both axes); `lut`: the 256 output values; both built by the caller (locate_amd/data.py) so that
+ *      nothing depends on how the device rounds.  `workspace`: locate_input_workspace_bytes(n, H, W) bytes, need not be zeroed.
+ *      The caller guarantees idx[i] < N and crops inside the image with side in [side_lo, side_hi]; a record that breaks this
+ *      leaves its output untouched. ---- */
+size_t locate_input_param_record_bytes(void);
+int locate_input_mean_blocks(int H, int W);      /* blocks per sample of the contrast pass = int32 words of workspace per sample */
+size_t locate_input_workspace_bytes(int n, int H, int W);
+int locate_input_transform(const void* store, int N, int H, int W, const int32_t* idx, const void* params, int n, int n_first,
+                           const int32_t* coef, int side_lo, int side_hi, int ktaps, const float* lut, int S, float* out_first,
+                           float* out_rest, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

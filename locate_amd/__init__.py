@@ -10,3 +10,4 @@ from .models import Discriminator, Generator, get_model, init, parameter_count  
 from .optim import Nadam  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .train import TrainLoop, TrainStep  # noqa: F401
+from .data import DeviceImageStore, InputPipeline, draw_params, prepare_folder  # noqa: F401

@@ -123,6 +123,10 @@ PROTOTYPES = {
     "locate_nadam_step": (c_i, [c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_p]),
     "locate_d_loss": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "locate_g_loss": (c_i, [c_p, c_i, c_p, c_p, c_p]),
+    "locate_input_param_record_bytes": (c_sz, []),
+    "locate_input_mean_blocks": (c_i, [c_i, c_i]),
+    "locate_input_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "locate_input_transform": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
 }
 
 
