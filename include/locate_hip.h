@@ -361,6 +361,23 @@ int locate_input_transform(const void* store, int N, int H, int W, const int32_t
                            const int32_t* coef, int side_lo, int side_hi, int ktaps, const float* lut, int S, float* out_first,
                            float* out_rest, void* workspace, void* stream);
 
+/* ---- training monitor (main.py:194-225: the reference's sample picture, which it makes on the host with torchvision's
+ *      make_grid(padding, normalize=True) and matplotlib's imsave).  x: fp32 [n, 3, S, S], contiguous, device memory.
+ *      locate_image_range: range = {min(x), max(x)} over all n_elems values (both NaN if x holds a NaN); exact in any order, no
+ *      atomics on values.  `workspace`: locate_image_range_workspace_bytes() bytes, need not be zeroed.
+ *      locate_image_grid: the tiled picture.  xmaps = min(nrow, n), ymaps = ceil(n / xmaps), GH = (S + padding) ymaps + padding,
+ *      GW = (S + padding) xmaps + padding; image k at row (k / xmaps)(S + padding) + padding, column (k % xmaps)(S + padding) +
+ *      padding; every other pixel is pad_value (not normalised; meant to lie in [0, 1]).  Per value, in fp32 IEEE operations:
+ *      v = (min(max(x, lo), hi) - lo) / d with d = (float) max((double) hi - (double) lo, 1e-5) when `divisor` is 0, else d =
+ *      divisor (a caller-supplied range: the caller takes hi - lo from its own doubles); byte = (uint8) (v * 255.0f), truncated.
+ *      grid_f32 [3, GH, GW] (what make_grid returns) and grid_u8 [GH, GW, 4] (RGBA, alpha 255: what imsave encodes): either may
+ *      be null, not both.  `range` is device memory {lo, hi}: locate_image_range's output or the caller's bounds.  A non-finite
+ *      x gives unspecified bytes. ---- */
+size_t locate_image_range_workspace_bytes(void);
+int locate_image_range(const float* x, int64_t n_elems, float* range, void* workspace, void* stream);
+int locate_image_grid(const float* x, int n, int S, int nrow, int padding, float pad_value, const float* range, float divisor,
+                      float* grid_f32, uint8_t* grid_u8, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,3 +11,12 @@ from .optim import Nadam  # noqa: F401
 from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .train import TrainLoop, TrainStep  # noqa: F401
 from .data import DeviceImageStore, InputPipeline, draw_params, prepare_folder  # noqa: F401
+from .monitor import LossHistory, Sampler, image_grid  # noqa: F401
+
+
+def __getattr__(name):
+    # `Trainer` is resolved on first use, so that `python -m locate_amd.run` does not find its module imported already
+    if name == "Trainer":
+        from .run import Trainer
+        return Trainer
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -127,6 +127,9 @@ PROTOTYPES = {
     "locate_input_mean_blocks": (c_i, [c_i, c_i]),
     "locate_input_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "locate_input_transform": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
+    "locate_image_range_workspace_bytes": (c_sz, []),
+    "locate_image_range": (c_i, [c_p, c_i64, c_p, c_p, c_p]),
+    "locate_image_grid": (c_i, [c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_p, c_p, c_p]),
 }
 
 

@@ -218,12 +218,21 @@ class Generator(_NetBase):
 
     def forward(self, function_input):
         self._sn_prologue()
-        # the constant noise map repeated over the batch (models.py:62): a copy that only changes with the map or the batch size
-        key = (function_input.size(0), self.noise.data_ptr(), self.noise._version)
-        cached = self.__dict__.get("_noise_batch")
+        # the constant noise map repeated over the batch (models.py:62): a copy that only changes with the map.  ONE tensor per
+        # batch size, kept for the life of the module and refreshed in place: a captured hipGraph reads its batch size's copy
+        # by address, and a forward at another batch size between two replays (locate_amd.monitor.Sampler) must not free it.
+        batch = function_input.size(0)
+        key = (self.noise.data_ptr(), self.noise._version)
+        copies = self.__dict__.setdefault("_noise_batch", {})
+        cached = copies.get(batch)
         if cached is None or cached[0] != key:
-            cached = (key, self.noise.expand(function_input.size(0), -1, -1, -1).contiguous())
-            self.__dict__["_noise_batch"] = cached
+            expanded = self.noise.detach().expand(batch, -1, -1, -1)
+            if cached is not None and cached[1].device == self.noise.device and cached[1].dtype == self.noise.dtype:
+                cached[1].copy_(expanded)
+                cached = (key, cached[1])
+            else:
+                cached = (key, expanded.contiguous())
+            copies[batch] = cached
         expanded_noise = cached[1]
         conv_out = self.conv_block(self.input_block(expanded_noise), function_input)
         return ops.tanh(self.out_conv(conv_out))

@@ -1,0 +1,283 @@
+"""The reference's outer loop (main.py:100-236) over `InputPipeline`, `TrainLoop` and the training monitor: epochs whose
+schedule grows with the epoch number, sub-passes over the data, a sample picture every `image_intervall` iterations and at the
+end of every pass, the loss curves and a checkpoint after every epoch.  Host glue only - everything it calls computes on the GPU.
+
+    python -m locate_amd.run --store FILE.npy --image-size S --batch B --out DIR [--epochs N] [--max-iterations N]
+                             [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
+
+Differences from the reference, all additions:
+  * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
+    the input pipeline's state, the fixed latents, the latent generator's state, the loss history) and the checkpoint files of
+    `locate_amd.checkpoint` are written after every epoch and whenever `max_iterations` stops the run, and a resumed run continues
+    the uninterrupted one's trajectory;
+  * the run ends after `epochs` epochs (the reference loops for ever) or after `max_iterations` iterations in all;
+  * every iteration that steps the optimizers is recorded for the loss curves (a record is two small launches and no host read);
+    the reference appends only the values it prints.  The progress line at `print_every` is the only place a loss is read on
+    the host;
+  * the per-iteration latents come from a generator of the trainer's own, so that its state can be saved."""
+import argparse
+import os
+import sys
+import time
+from datetime import timedelta
+
+import torch
+
+from .checkpoint import load_checkpoint, save_checkpoint
+from .monitor import LossHistory, Sampler
+from .train import TrainLoop
+
+MAIN_N = 2 ** 10          # libs/config.py:67
+STATE_FILE = "trainer.torch"
+
+
+# ---- the reference's schedule (libs/config.py:19-30, main.py:109-116), per 0-based epoch e ----
+def reference_miniter(e, minibatches=8):
+    return int((e + 1) * minibatches)
+
+
+def reference_subepochs(e):
+    return (e + 1) ** 2
+
+
+def reference_print_every(batch, main_n=MAIN_N):
+    return max(1, main_n // max(batch, 64))
+
+
+def reference_image_interval(batch, main_n=MAIN_N):
+    return max(1, 16 * main_n // batch)
+
+
+def picture_name(sub, i, subepochs, batches):
+    """`{sub+1:0{sub_len}d}-{i:0{batch_len}d}.png`, or `...-END.png` for i = None (main.py:204-205, 221)."""
+    head = "%0*d" % (len(str(subepochs)), sub + 1)
+    return head + ("-END.png" if i is None else "-%0*d.png" % (len(str(batches)), i))
+
+
+class Trainer:
+    """step: a `TrainStep`; pipeline: an `InputPipeline`; out: the output folder.
+
+    Schedule per epoch e (0-based): `miniter_function(e)` (default (e + 1) * minibatches, minibatches = step.minibatches),
+    `subepoch_function(e)` (default (e + 1)^2), `print_every_function(batch)` (default max(1, MAIN_N // max(batch, 64))) and
+    `image_interval_function(batch)` (default max(1, 16 * MAIN_N // batch)).  In every sub-pass the batch counter i restarts at 1;
+    the print and the sample checks sit inside `if i % miniter == 0`, as in the reference.
+
+    Files: `out/{e+1}/{sub+1}-{i}.png` and `...-END.png` (zero-padded like the reference's), `out/error/{e+1}.json` (and .svg
+    where matplotlib imports), the checkpoint files and `out/trainer.torch`.
+
+    graphed=True replays the iteration as hipGraphs (`GraphedTrainStep`).  It is accepted only when miniter == 1 and diters == 1
+    in every epoch of the run - so `epochs` must be given - and raises ValueError otherwise.  SIDE EFFECT, as documented on
+    `GraphedTrainStep`: building it runs max(warmup, 2) = 2 REAL training iterations eagerly on the run's first batch before
+    the capture, so the weights, u / v and Nadam states advance by two steps more than the iteration count says (again after
+    every resume).
+
+    sampler_options: passed to `Sampler` (nrow, padding, advance_spectral_norm - True, the reference's behaviour, by default).
+    log: a callable taking one line of text (the progress line), or None."""
+
+    def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
+                 mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
+                 print_every_function=None, image_interval_function=None, sampler_options=None, log=None):
+        self.step, self.pipeline, self.out = step, pipeline, str(out)
+        self.gen, self.dis = step.gen, step.dis
+        self.batch = pipeline.batch
+        self.epochs = None if epochs is None else int(epochs)
+        self.max_iterations = None if max_iterations is None else int(max_iterations)
+        m = step.minibatches if minibatches is None else int(minibatches)
+        self.miniter_function = miniter_function or (lambda e: reference_miniter(e, m))
+        self.subepoch_function = subepoch_function or reference_subepochs
+        self.print_every = (print_every_function or reference_print_every)(self.batch)
+        self.image_interval = (image_interval_function or reference_image_interval)(self.batch)
+        if self.print_every < 1 or self.image_interval < 1:
+            raise ValueError("print_every and image_interval must be >= 1")
+        self.diters = int(diters)
+        self.graphed = bool(graphed)
+        if self.graphed:
+            if self.epochs is None:
+                raise ValueError("graphed=True needs `epochs`: the whole schedule must be known to be miniter == 1")
+            bad = [e for e in range(self.epochs) if self.miniter_function(e) != 1]
+            if bad or self.diters != 1:
+                raise ValueError("graphed=True replays whole iterations: miniter == 1 and diters == 1 throughout "
+                                 "(miniter is %d in epoch %d, diters %d)" % (self.miniter_function(bad[0]) if bad else 1,
+                                                                            bad[0] + 1 if bad else 1, self.diters))
+        self.loop = TrainLoop(step, 1, self.diters)
+        self.device = next(self.gen.parameters()).device
+        self._sampler_args = dict(fixed_noise=fixed_noise, images=images, seed=seed, **(sampler_options or {}))
+        self._sampler = None
+        self.history = LossHistory(mean_window)
+        self._seed = int(seed)
+        self._latent_rng = None
+        self.log = log
+        self.epoch, self.sub, self.i, self.iterations = 0, 0, 0, 0
+        self._runner = None
+        self.written = []
+
+    # ---- device-side helpers, made on first use (the schedule can be inspected without a GPU) ------------------
+    @property
+    def sampler(self):
+        if self._sampler is None:
+            self._sampler = Sampler(self.gen, **self._sampler_args)
+        return self._sampler
+
+    @property
+    def _latent_gen(self):
+        if self._latent_rng is None:
+            self._latent_rng = torch.Generator(device=self.device)
+            self._latent_rng.manual_seed(self._seed + 1)
+        return self._latent_rng
+
+    # ---- schedule -------------------------------------------------------------------------------------------
+    def schedule(self, e):
+        """{miniter, subepochs, print_every, image_interval} of 0-based epoch e"""
+        return {"miniter": int(self.miniter_function(e)), "subepochs": int(self.subepoch_function(e)),
+                "print_every": self.print_every, "image_interval": self.image_interval}
+
+    def picture_path(self, e, sub, i):
+        return os.path.join(self.out, str(e + 1), picture_name(sub, i, int(self.subepoch_function(e)), self.pipeline.batches_per_epoch))
+
+    # ---- state ----------------------------------------------------------------------------------------------
+    def save_state(self):
+        """The checkpoint files and trainer.torch (written last: it names a state the other files already hold)."""
+        files = save_checkpoint(self.out, self.gen, self.dis, self.step.gen_opt, self.step.dis_opt)
+        state = {"epoch": self.epoch, "sub": self.sub, "i": self.i, "iterations": self.iterations,
+                 "pipeline": self.pipeline.state_dict(), "fixed_noise": self.sampler.fixed_noise.detach().cpu(),
+                 "latent_state": self._latent_gen.get_state(), "history": self.history.state_dict()}
+        path = os.path.join(self.out, STATE_FILE)
+        torch.save(state, path + ".tmp")
+        os.replace(path + ".tmp", path)
+        return files + [path]
+
+    def resume(self):
+        """Continue from what save_state() left in `out`."""
+        state = torch.load(os.path.join(self.out, STATE_FILE), map_location="cpu", weights_only=True)
+        load_checkpoint(self.out, self.gen, self.dis, self.step.gen_opt, self.step.dis_opt)
+        self.epoch, self.sub, self.i, self.iterations = (int(state[k]) for k in ("epoch", "sub", "i", "iterations"))
+        self.pipeline.load_state_dict(state["pipeline"])
+        noise = state["fixed_noise"]
+        if tuple(noise.shape) != tuple(self.sampler.fixed_noise.shape):
+            raise ValueError("trainer.torch holds fixed latents of shape %s, this run's are %s" % (tuple(noise.shape), tuple(self.sampler.fixed_noise.shape)))
+        self.sampler.fixed_noise.copy_(noise)
+        self._latent_gen.set_state(state["latent_state"])
+        self.history.load_state_dict(state["history"])
+        return self
+
+    # ---- the loop -------------------------------------------------------------------------------------------
+    def _iteration(self):
+        latent_shape = (self.batch, self.gen.g_in)
+        if not self.graphed:
+            latent = torch.randn(latent_shape, device=self.device, generator=self._latent_gen)          # main.py:142
+            real, aug = self.pipeline.next_batch()
+            return self.loop.iteration(latent, real, aug)
+        if self._runner is None:
+            from .graph import GraphedTrainStep
+            latent = torch.randn(latent_shape, device=self.device, generator=self._latent_gen)
+            real, aug = self.pipeline.next_batch()
+            self._runner = GraphedTrainStep(self.step, latent, real, aug)          # runs two real iterations on this batch
+            return self._runner.replay()
+        lat, real, aug = self._runner.inputs
+        lat.copy_(torch.randn(latent_shape, device=self.device, generator=self._latent_gen))
+        self.pipeline.next_batch(out_real=real, out_aug=aug)          # written straight into the graphs' static inputs
+        return self._runner.replay()
+
+    def _progress(self, e, sub, i, first, subepochs, batches, started):
+        """first: the position this call of run() entered the sub-pass at (not 0 after a resume): the rate counts from there"""
+        pairs = self.history.flush()          # the one host read of the losses
+        if self.log is None or not (self.history.d and self.history.g):
+            return
+        rate = (i - first) / max(time.time() - started, 1e-9)
+        eta = str(timedelta(seconds=int((batches - i) / rate)))
+        d, g = (pairs[-1] if pairs else (self.history.d[-1], self.history.g[-1]))
+        self.log("[%d][%d/%d][%*d/%d] | Rate: %.2f Img/s - %.2f Upd/s | D:%9.4f - G:%9.4f| ETA: %s"
+                 % (e + 1, sub + 1, subepochs, len(str(batches)), i, batches, rate * self.batch, rate, d, g, eta))
+
+    def _picture(self, e, sub, i):
+        path = self.picture_path(e, sub, i)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        self.written.append(self.sampler.save(path))
+
+    def run(self):
+        """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
+        returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
+        batches = self.pipeline.batches_per_epoch
+        while self.epochs is None or self.epoch < self.epochs:
+            e = self.epoch
+            sched = self.schedule(e)
+            miniter, subepochs = sched["miniter"], sched["subepochs"]
+            self.loop.miniter = miniter
+            while self.sub < subepochs:
+                started, first = time.time(), self.i
+                self.loop.i = self.i          # i restarts at 1 in every sub-pass (main.py:140)
+                while self.i < batches:
+                    if self.max_iterations is not None and self.iterations >= self.max_iterations:
+                        self.written += self.save_state()
+                        return self.iterations
+                    out = self._iteration()
+                    self.i += 1
+                    self.iterations += 1
+                    i = self.i
+                    if i % miniter == 0:          # main.py:158
+                        self.history.record(out)
+                        if i % sched["print_every"] == 0:          # :174
+                            self._progress(e, self.sub, i, first, subepochs, batches, started)
+                        if i % sched["image_interval"] == 0:          # :194
+                            self._picture(e, self.sub, i)
+                self._picture(e, self.sub, None)          # :213-225
+                self.sub, self.i = self.sub + 1, 0
+            self.written += self.history.save(os.path.join(self.out, "error"), e + 1)          # :226-234
+            self.history = LossHistory(self.history.mean_window)          # dhist / ghist start empty in every epoch (:107-108)
+            self.epoch, self.sub = e + 1, 0
+            self.written += self.save_state()          # :235-236
+        return self.iterations
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m locate_amd.run", description="Train on a prepared image store and watch the run.")
+    ap.add_argument("--store", required=True, help="uint8 [N, H, W, 3] .npy file (locate_amd.data.prepare_folder)")
+    ap.add_argument("--image-size", type=int, required=True)
+    ap.add_argument("--batch", type=int, required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--epochs", type=int, default=None, help="default: until interrupted, like the reference")
+    ap.add_argument("--max-iterations", type=int, default=None, help="stop (and save) after this many iterations in all")
+    ap.add_argument("--images", type=int, default=64, help="images in the sample picture")
+    ap.add_argument("--seed", type=int, default=999)
+    ap.add_argument("--minibatches", type=int, default=8, help="MINIBATCHES of the reference; 1 gives miniter = 1 in the first epoch")
+    ap.add_argument("--diters", type=int, default=1)
+    ap.add_argument("--graph", action="store_true", help="replay the iteration as hipGraphs (needs miniter = diters = 1 throughout)")
+    ap.add_argument("--resume", action="store_true", help="continue from the files in --out")
+    ap.add_argument("--keep-spectral-norm", action="store_true",
+                    help="sampling leaves the generator's u / v untouched (the reference's sampling pass advances them)")
+    args = ap.parse_args(argv)
+
+    from . import DeviceImageStore, Discriminator, Generator, InputPipeline, NetConfig, TrainStep, get_model
+    from ._lib import require_gpu
+    require_gpu()
+    dev = torch.device("cuda:0")
+    cfg = NetConfig(image_size=args.image_size, seed=args.seed)
+    torch.manual_seed(cfg.seed)
+    gen, gen_opt = get_model(Generator(cfg), cfg.glr, dev, cfg)
+    dis, dis_opt = get_model(Discriminator(cfg), cfg.dlr, dev, cfg)
+    gen.batched_spectral_norm = dis.batched_spectral_norm = True
+    step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches)
+    pipeline = InputPipeline(DeviceImageStore(args.store, dev), args.image_size, args.batch, seed=args.seed)
+    if not args.resume:
+        os.makedirs(args.out, exist_ok=True)
+
+    def log(line):
+        sys.stdout.write("\r" + line)
+        sys.stdout.flush()
+
+    trainer = Trainer(step, pipeline, args.out, epochs=args.epochs, max_iterations=args.max_iterations, images=args.images,
+                      seed=args.seed, diters=args.diters, graphed=args.graph, log=log,
+                      sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
+    if args.resume:
+        trainer.resume()
+    else:
+        real, aug = InputPipeline(pipeline.store, args.image_size, min(64, len(pipeline.store)), seed=args.seed + 2).next_batch()
+        trainer.sampler.preview(real, os.path.join(args.out, "0.png"))          # main.py:45-48
+        trainer.sampler.preview(aug, os.path.join(args.out, "1.png"))
+    n = trainer.run()
+    print("\n%d iterations, state in %s" % (n, args.out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
