@@ -10,12 +10,13 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "liblocate_hip.so")
-# debug variant: the same objects, except that conv.hip is compiled with -DLOCATE_DEBUG_KNOBS (the LOCATE_DISABLE kernel-flavour
-# switch used by tests/test_gpu_ops.py::test_bf16x6_kernels_match_fp32_mfma_kernels and the A/B tools).  Loaded only when
+# debug variant: the same objects, except that every source that calls path_disabled / knob_int (igemm.h) is compiled with
+# -DLOCATE_DEBUG_KNOBS (the LOCATE_DISABLE kernel-flavour switch used by
+# tests/test_gpu_ops.py::test_bf16x6_kernels_match_fp32_mfma_kernels and the A/B tools).  Loaded only when
 # LOCATE_HIP_DEBUG_LIBRARY=1 is set before `import locate_amd`; the product library has no such switch compiled in.
 LIB_DBG = os.path.join(CSRC, "liblocate_hip_dbg.so")
-DBG_SOURCES = ["conv.hip", "convwin.hip"]
-SOURCES = ["runtime.hip", "elementwise.hip", "norm.hip", "softmax.hip", "resample.hip", "spectral.hip", "conv.hip", "convwin.hip", "convfp8.hip",
+DBG_SOURCES = ["conv.hip", "convwgrad.hip", "convwin.hip"]
+SOURCES = ["runtime.hip", "elementwise.hip", "norm.hip", "softmax.hip", "resample.hip", "spectral.hip", "conv.hip", "convpack.hip", "convwgrad.hip", "convwin.hip", "convfp8.hip",
            "grouped.hip", "nadam.hip", "loss.hip", "finalise.hip", "parallel.hip", "input.hip", "grid.hip"]
 ARCH = "gfx950"
 

@@ -233,9 +233,5 @@ __global__ void __launch_bounds__(256, (WGM * TM > 4 ? 2 : 3)) conv_igemm_fp8_ke
 }
 
 void launch_fp8_igemm(const IgParams& p, dim3 grid, int bm, hipStream_t st) {
-    if (bm == 192) conv_igemm_fp8_kernel<2, 2, 3, 2><<<grid, 256, 0, st>>>(p);
-    else if (bm == 128) conv_igemm_fp8_kernel<2, 2, 2, 2><<<grid, 256, 0, st>>>(p);
-    else if (bm == 96) conv_igemm_fp8_kernel<1, 4, 3, 1><<<grid, 256, 0, st>>>(p);
-    else if (bm == 64) conv_igemm_fp8_kernel<1, 4, 2, 1><<<grid, 256, 0, st>>>(p);
-    else conv_igemm_fp8_kernel<1, 4, 1, 1><<<grid, 256, 0, st>>>(p);
+    with_tile<true>(bm, [&](auto t) { using T = decltype(t); conv_igemm_fp8_kernel<T::wgm, T::wgn, T::tm, T::tn><<<grid, 256, 0, st>>>(p); });
 }

@@ -14,7 +14,7 @@
 // bytes per lane.  For stride-2 gathers the window's columns are stored de-interleaved by parity (even columns, then odd), which
 // keeps the fragment reads of neighbouring output columns on neighbouring chunks (conflict-free ds_read_b128).
 //
-// The weight operand comes from a WINDOW PANEL (conv.hip, pack_win_body): chunk rows in "unit" order u = c8g * Tp + t, so that
+// The weight operand comes from a WINDOW PANEL (convpack.hip, pack_win_body): chunk rows in "unit" order u = c8g * Tp + t, so that
 // the 16-deep MFMA slice (units 2i, 2i + 1 - lane half h takes unit 2i + h) pairs two taps of the same 8 channels (or, for a
 // single-tap layer, two 8-channel groups).  One stage = U = 2 SL units; one window = 8 channels x every tap = NG stages (a
 // single-tap layer: U channel groups, one stage).  The next window's loads are spread over the current window's stages.

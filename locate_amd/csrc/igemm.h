@@ -1,5 +1,6 @@
-// Shared declarations of the dense-contraction kernels (conv.hip: implicit-GEMM gather kernels, panel packing, weight
-// gradients; convwin.hip: the LDS-window kernels): panel layout, launch parameters, operand splits, the common epilogue.
+// Shared declarations of the dense-contraction kernels (conv.hip: implicit-GEMM gather kernels, their planning and entry points;
+// convpack.hip: panel packing; convwgrad.hip: weight gradients; convwin.hip: the LDS-window kernels; convfp8.hip: fp8 operands):
+// geometry, tile table, panel layout, launch parameters, operand splits, the common epilogue.
 #pragma once
 #include "common.h"
 #include <cstdlib>
@@ -50,7 +51,47 @@ static int geom_check(const ConvGeom& g, const char* who) {
     return LOCATE_OK;
 }
 
+// geom = {B, C, H, W, M, KH, KW, stride, pad_h, pad_w, OH, OW} of the regular convolution R (the C ABI's form)
+static inline ConvGeom make_geom(const int* g) {
+    ConvGeom c;
+    c.B = g[0]; c.C = g[1]; c.H = g[2]; c.W = g[3]; c.M = g[4]; c.KH = g[5]; c.KW = g[6];
+    c.stride = g[7]; c.pad_h = g[8]; c.pad_w = g[9]; c.OH = g[10]; c.OW = g[11];
+    return c;
+}
+
 static inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+
+// ---------------------------------------------------------------------------------------------
+// Block tiles of the four-wave contraction kernels (gather, fp8, weight gradient): BM rows x 128 columns.  pick_bm takes the
+// height that pads M least (the taller one on a tie); the callers add their own conditions for the tall 192-row tile.
+// with_tile turns the runtime height into the compile-time wave grid WGM x WGN and wave tile TM x TN (in 32 x 32 fragments):
+// f(Tile<...>{}).  TALL = false: kernels without a 192-row instantiation (the fp32-MFMA ones).
+// ---------------------------------------------------------------------------------------------
+static inline int pick_bm(int M) {
+    const int cands[4] = {128, 96, 64, 32};
+    int best = 128, best_pad = 1 << 30;
+    for (int i = 0; i < 4; ++i) {
+        const int pad = round_up(M, cands[i]);
+        if (pad < best_pad) { best_pad = pad; best = cands[i]; }
+    }
+    return best;
+}
+
+template <int WGM, int WGN, int TM, int TN>
+struct Tile {
+    static constexpr int wgm = WGM, wgn = WGN, tm = TM, tn = TN;
+};
+
+template <bool TALL, class F>
+static inline void with_tile(int bm, F&& f) {
+    if constexpr (TALL) {          // (discarded, not merely skipped, otherwise: f is never instantiated for the tall tile)
+        if (bm == 192) return f(Tile<2, 2, 3, 2>{});
+    }
+    if (bm == 128) f(Tile<2, 2, 2, 2>{});
+    else if (bm == 96) f(Tile<1, 4, 3, 1>{});
+    else if (bm == 64) f(Tile<1, 4, 2, 1>{});
+    else f(Tile<1, 4, 1, 1>{});
+}
 
 // ---------------------------------------------------------------------------------------------
 // Weight panel of one phase (all sections in 4-byte units, one buffer):
@@ -89,6 +130,22 @@ struct PackArgs {
     // header, filled by win_absmax_jobs_kernel) instead of AMAX_WORDS words.
     int win, Tp, urows, wmax_single;
 };
+
+// Panel packing (convpack.hip).  conv.hip plans a panel - one PackArgs per phase - and hands the batch over: launch_pack packs it
+// now, make_pack_job turns it into the record of a batched launch (locate_conv_pack_job / locate_conv_pack_panels).
+#define PACK_MAX_TAPS 32
+struct PackBatch {
+    PackArgs ph[4];
+};
+// One packing job = all phases of one panel; `kind` selects the body, (gx, gy) is its virtual grid.
+struct PackJob {
+    PackBatch batch;
+    int nphase, kind;          // kind 0: transpose, 1: adjoint, 2: generic, 3: adjoint, direct form, 4: window panel
+    int gx, gy;
+    int block_start, pad;      // first block of this job inside a batched launch
+};
+PackJob make_pack_job(const PackBatch& b, int nphase);
+int launch_pack(const PackBatch& b, int nphase, hipStream_t st, const char* who);
 
 // fmt 0: the split section holds the three bf16 planes; fmt 1 ("fp16 pieces", see conv_igemm_bx6_kernel NP = 2): a 4-dword
 // header {absmax bits of this phase's weights, 0, 0, 0} followed by TWO fp16 planes of the weights times 2^k(absmax)
@@ -543,22 +600,13 @@ static void fastdiv_make(unsigned d, unsigned* mul, int* s1, int* s2) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Window kernels (convwin.hip): shared planning (conv.hip packs the panels and fills the phase tables, convwin.hip launches)
+// Window kernels (convwin.hip): shared planning (conv.hip plans the panels and fills the phase tables, convpack.hip packs, convwin.hip launches)
 // ---------------------------------------------------------------------------------------------
 #define WIN_TAIL_UNITS 16          // zero chunk rows behind the last unit: the A prefetch runs two stages (<= 2 x 8 rows) ahead
 
 // Tile of the window kernels: rows BM x columns BN of four waves.  Every wave tile is at least 64 columns wide (two B fragments per
 // A fragment read): 192 x 128 (waves 96 x 64) and 128 x 128 (64 x 64) for the wide layers, 96 / 64 / 32 rows x 256 columns below.
-static inline int win_pick_bm(int M) {
-    if (M >= 192 && M % 192 == 0) return 192;
-    const int cands[4] = {128, 96, 64, 32};
-    int best = 128, best_pad = 1 << 30;
-    for (int i = 0; i < 4; ++i) {
-        const int pad = (M + cands[i] - 1) / cands[i] * cands[i];
-        if (pad < best_pad) { best_pad = pad; best = cands[i]; }
-    }
-    return best;
-}
+static inline int win_pick_bm(int M) { return (M >= 192 && M % 192 == 0) ? 192 : pick_bm(M); }
 static inline int win_pick_bn(int bm) { return bm >= 128 ? 128 : 256; }
 // 16-deep slices per stage: two while the padding of the unit count (taps, or 8-channel groups of a single-tap layer) to a multiple
 // of four stays under 15 %, else one

@@ -21,7 +21,7 @@ struct NadamTensor {
     long long n;
     unsigned* absmax;  // nullable: AMAX_WORDS words that receive the largest magnitude of the UPDATED tensor (bit pattern,
                        // spread like every other absmax slot, common.h) - what the fp16-piece weight panels are scaled by;
-                       // re-packing them then needs no pass of its own over the weights (conv.hip, direct packing)
+                       // re-packing them then needs no pass of its own over the weights (convpack.hip, direct packing)
 };
 
 struct NadamCoef {

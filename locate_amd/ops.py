@@ -347,8 +347,8 @@ class Runtime:
         self._fin_sums = []
         self._fin_chan = []
         self._fin_norm = []
-        self._fin_wgrad = []             # packed SkwRec records (conv.hip): the pass's small-map weight gradients
-        self._fin_slab = []              # packed SlabRec records (conv.hip): the split reductions of its other weight gradients
+        self._fin_wgrad = []             # packed SkwRec records (convwgrad.hip): the pass's small-map weight gradients
+        self._fin_slab = []              # packed SlabRec records (convwgrad.hip): the split reductions of its other weight gradients
         self._streams = {}               # streams on which this pass queued deferred work / produced late gradients
         self._homes_taken = set()        # parameters whose bucket home (see _grad_home) a gradient of this pass already occupies
 
@@ -1219,7 +1219,7 @@ def refresh_panels(params):
     if not stale:
         return
     # the optimizer kernel leaves the updated weights' largest magnitude per tensor (optim.Nadam._absmax_words, stamped with the
-    # parameter version it belongs to): fp16-piece panels are then re-packed in one pass (conv.hip, direct form).  Anything else -
+    # parameter version it belongs to): fp16-piece panels are then re-packed in one pass (convpack.hip, direct form).  Anything else -
     # weights changed by other means, bf16-piece panels - takes the two-pass form.
     def wmax_of(w):
         hold = w.__dict__.get("_locate_wmax") if DIRECT_REPACK else None

@@ -1,6 +1,6 @@
 #!/bin/bash
 # VGPRs / scratch / occupancy / LDS of every kernel of one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
-# usage: tools/kernel_resources.sh locate_amd/csrc/conv.hip [name filter]
+# usage: tools/kernel_resources.sh locate_amd/csrc/conv.hip [name filter]     (or convwgrad.hip, convpack.hip, convwin.hip, ...)
 F=$1; PAT=${2:-.}
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -I "$(dirname "$F")" -c "$F" -o /dev/null -Rpass-analysis=kernel-resource-usage 2>&1 \
  | python3 -c "
