@@ -224,8 +224,7 @@ __global__ void __launch_bounds__(64 * NW, (NW == 8 ? 1 : (WGM * TM > 4 ? 2 : ((
         const int kb_ = f16_scale_exp(absmax_read(p.b_absmax));
         const int ka_ = f16_scale_exp(__builtin_amdgcn_readfirstlane(*ph.a_absmax));
         b_scale = pow2f(kb_);
-        a_unscale = pow2f(-ka_);
-        b_unscale = pow2f(-kb_);
+        unscale_pair(ka_, kb_, a_unscale, b_unscale);
     }
 
     f32x16 acc[TM][TN];
@@ -394,8 +393,8 @@ __global__ void __launch_bounds__(64 * NW, (NW == 8 ? 1 : (WGM * TM > 4 ? 2 : ((
         }
         __syncthreads();
     }
-    if constexpr (NP == 2) {       // undo the two power-of-two scales, one after the other (each exact; their product may not be
-                                   // a normal fp32 number): whatever leaves this block - output or split-K partial - is unscaled
+    if constexpr (NP == 2) {       // undo the two power-of-two scales in two exact steps of half the total exponent each (unscale_pair:
+                                   // neither their product nor acc * one of them need be a normal fp32 number): whatever leaves this block - output or split-K partial - is unscaled
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll

@@ -62,7 +62,9 @@ __global__ void __launch_bounds__(256, (WGM * TM > 4 ? 2 : 3)) conv_igemm_fp8_ke
     igemm_col_scales<WGM, WGN, TM, TN>(p, ph, col_scale, N, n0, wn, lane);
     const int kb_ = f8_scale_exp(absmax_read(p.b_absmax));
     const int ka_ = f8_scale_exp(__builtin_amdgcn_readfirstlane(*ph.a_absmax));
-    const float b_scale = pow2f(kb_), a_unscale = pow2f(-ka_), b_unscale = pow2f(-kb_);
+    const float b_scale = pow2f(kb_);
+    float a_unscale, b_unscale;
+    unscale_pair(ka_, kb_, a_unscale, b_unscale);
 
     f32x16 acc[TM][TN];
 #pragma unroll

@@ -308,15 +308,15 @@ __global__ void __launch_bounds__(256, (WGM * TM > 4 ? 2 : 3)) conv_wgrad_bx6_ke
         const float gmax = __uint_as_float(absmax_read(p.g_absmax)) * fmaxf(fmaxf(gs0, gs1), fmaxf(gs2, gs3));
         const int kg_ = f16_scale_exp(__float_as_uint(gmax) + (p.gscale_bg > 0 ? 0x00800000u : 0u));    // (product rounded: one binade of slack)
         const int kx_ = f16_scale_exp(absmax_read(p.x_absmax));
-        g_scale = pow2f(kg_); g_unscale = pow2f(-kg_);
-        x_scale = pow2f(kx_); x_unscale = pow2f(-kx_);
+        g_scale = pow2f(kg_); x_scale = pow2f(kx_);
+        unscale_pair(kg_, kx_, g_unscale, x_unscale);
     }
     if constexpr (NP == 4) {
         const float gmax = __uint_as_float(absmax_read(p.g_absmax)) * fmaxf(fmaxf(gs0, gs1), fmaxf(gs2, gs3));
         const int kg_ = f8_scale_exp(__float_as_uint(gmax) + (p.gscale_bg > 0 ? 0x00800000u : 0u));
         const int kx_ = f8_scale_exp(absmax_read(p.x_absmax));
-        g_scale = pow2f(kg_); g_unscale = pow2f(-kg_);
-        x_scale = pow2f(kx_); x_unscale = pow2f(-kx_);
+        g_scale = pow2f(kg_); x_scale = pow2f(kx_);
+        unscale_pair(kg_, kx_, g_unscale, x_unscale);
     }
     // a pair of values rounded to e4m3: two bytes
     auto q8_pair = [](float v0, float v1) { return (unsigned short)(__builtin_amdgcn_cvt_pk_fp8_f32(v0, v1, 0, false) & 0xffff); };
@@ -811,7 +811,7 @@ __global__ void __launch_bounds__(256) pw_wgrad_kernel(const PwParams p) {
     if constexpr (NP == 2) {          // powers of two into fp16's range; the exact inverses go back in after the loop
         const int kx = f16_scale_exp(absmax_read(p.x_absmax)), kg = f16_scale_exp(absmax_read(p.g_absmax));
         x_scale = pow2f(kx); g_scale = pow2f(kg);
-        x_unscale = pow2f(-kx); g_unscale = pow2f(-kg);
+        unscale_pair(kg, kx, g_unscale, x_unscale);
     }
 
     f32x16 acc[TM][TN];

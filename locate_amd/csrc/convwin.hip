@@ -98,8 +98,7 @@ __global__ void __launch_bounds__(256, 2) conv_win_kernel(const IgParams p) {
         const int kb_ = f16_scale_exp(absmax_read(p.b_absmax));
         const int ka_ = f16_scale_exp(__builtin_amdgcn_readfirstlane(*ph.a_absmax));
         b_scale = pow2f(kb_);
-        a_unscale = pow2f(-ka_);
-        b_unscale = pow2f(-kb_);
+        unscale_pair(ka_, kb_, a_unscale, b_unscale);
     }
 
     f32x16 acc[TM][TN];
@@ -385,7 +384,7 @@ __global__ void __launch_bounds__(256, 2) conv_win_kernel(const IgParams p) {
         if (++g == NG) { g = 0; ++wrel; }
         __syncthreads();
     }
-    if constexpr (NP == 2) {       // undo the two power-of-two scales, one after the other (each exact)
+    if constexpr (NP == 2) {       // undo the two power-of-two scales in two exact steps (unscale_pair, igemm.h)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll

@@ -162,21 +162,35 @@ __device__ __forceinline__ size_t panel_split_offset_dev(int rows, int ld) { ret
 // - one binade below fp16's largest finite value, so that the two fp16 pieces of every element (11 + 11 significant bits)
 // stay normal numbers down to elements 2^-17 of the largest (below that the low piece goes subnormal: absolute error
 // <= 2^-25 on the scaled tensor, i.e. 2^-39 of its largest element).  Zero / denormal tensors: k = 0.  Clamped so that
-// 2^k and 2^-k are normal fp32 numbers.
+// 2^k and 2^-k are normal fp32 numbers (pow2f: |k| <= 126).  k = 14 - e runs from -113 (largest finite fp32 binade) upwards, so
+// the clamp only ever binds at +126, for tensors whose largest magnitude is below 2^-112: their pieces merely sit lower in
+// fp16's range.  (A tighter clamp, at +-100 say, would leave tensors of >= 2^115 scaled to >= 2^15: high pieces of inf.)
 __host__ __device__ __forceinline__ int f16_scale_exp(unsigned bits) {
     const int e = (int)((bits >> 23) & 0xffu) - 127;
     if (e == -127) return 0;
     const int k = 14 - e;
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
+    return k > 126 ? 126 : (k < -126 ? -126 : k);
 }
 // the same for e4m3 operands (largest finite value 448): absmax * 2^k in [2^7, 2^8)
 __host__ __device__ __forceinline__ int f8_scale_exp(unsigned bits) {
     const int e = (int)((bits >> 23) & 0xffu) - 127;
     if (e == -127) return 0;
     const int k = 7 - e;
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
+    return k > 126 ? 126 : (k < -126 ? -126 : k);          // (binds below 2^-119 only, see f16_scale_exp)
 }
 __device__ __forceinline__ float pow2f(int k) { return __uint_as_float((unsigned)(k + 127) << 23); }      // -126 <= k <= 127
+// The inverse of two operand scales 2^ka, 2^kb as two factors applied one after the other, acc = (acc * u1) * u2: 2^-(ka + kb)
+// need not be a normal fp32 number, and neither need acc * 2^-ka be (a gradient of 2^118 against activations of 2^3: the
+// accumulator of ~2^30 times 2^104 is inf, the result 2^125 is not).  Two halves of the total exponent: the intermediate lies
+// between the accumulator and the result, so it is finite and normal whenever both are.  Multiplications by powers of two are
+// exact while nothing leaves the normal range, so every NORMAL result has the bits (acc * 2^-ka) * 2^-kb gives where that
+// form's intermediate is normal too.  A result that is itself subnormal may be rounded in either step (twice, where the one
+// step that shrinks was the only rounding before): below 2^-126 the contractions promise no particular bits.
+__device__ __forceinline__ void unscale_pair(int ka, int kb, float& u1, float& u2) {
+    const int t = -(ka + kb), h = t >> 1;          // |ka|, |kb| <= 126: both halves within pow2f's range
+    u1 = pow2f(h);
+    u2 = pow2f(t - h);
+}
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
