@@ -196,8 +196,8 @@ LOCATE_API int locate_sn_power_iter(const float* w, float* u, float* v, float* s
     return LOCATE_OK;
 }
 
-// Batched form: `table` is a DEVICE array of `n_layers` records of 9 x 8 bytes:
-//   { w, u, v, sigma, wv, t, s, tpart (pointers), (h | wd << 32), (nchunk) } - see locate_sn_table_record_bytes().
+// Batched form: `table` is a DEVICE array of `n_layers` SnLayer records of 80 bytes:
+//   { w, u, v, sigma, wv, t, s, tpart (eight pointers), int h, wd, nchunk, pad } - see locate_sn_table_record_bytes().
 // max_h / max_wd: maxima over the table (grid sizing).  Four launches advance every layer.
 LOCATE_API size_t locate_sn_table_record_bytes(void) { return sizeof(SnLayer); }
 
