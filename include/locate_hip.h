@@ -378,6 +378,35 @@ int locate_image_range(const float* x, int64_t n_elems, float* range, void* work
 int locate_image_grid(const float* x, int n, int S, int nrow, int padding, float pad_value, const float* range, float divisor,
                       float* grid_f32, uint8_t* grid_u8, void* stream);
 
+/* ---- sliced Wasserstein distance between Laplacian-pyramid patch descriptors (Karras et al., "Progressive Growing of GANs",
+ *      section 5; the reference has no quality metric).  Every call is stateless, uses no atomics and returns the same bits from
+ *      call to call.  All tensors fp32, contiguous, device memory.
+ *      Pyramid: g = outer([1,4,6,4,1], [1,4,6,4,1]) / 256, borders mirrored without repeating the edge sample (-1 -> 1, -2 -> 2,
+ *      H -> H - 2, H + 1 -> H - 3).  pyr_down: x [planes, S, S] -> out [planes, S/2, S/2], out[i, j] = sum_ab g[a, b]
+ *      x[m(2i + a - 2), m(2j + b - 2)]; S even, >= 8.  pyr_residual: out = x - up(coarse), coarse [planes, S/2, S/2], up = coarse
+ *      written into the even positions of a zero map of size S and filtered with 4 g (mirror on that doubled grid); evaluated in
+ *      its polyphase form, the upsampled map is never stored; out may be x.
+ *      Descriptors: descriptor j of n = N P belongs to image j / P; pos int32 [n, 2] = (y, x) of its top-left corner in
+ *      [0, S - 7] (a record outside is clamped into it); element k = c 49 + dy 7 + dx is level[j / P, c, y + dy, x + dx], K = 147.
+ *      swd_stats: stats[6] = {mu_0, mu_1, mu_2, r_0, r_1, r_2}: per channel the mean and 1 / the population deviation over all
+ *      n 49 gathered values (patches overlap: not the statistic of the map), fp64 sums in a fixed order, each rounded once to fp32.
+ *      A constant channel gives a non-finite r; it is not guarded.  `workspace`: locate_swd_stats_workspace_bytes() bytes, 8-byte
+ *      aligned, need not be zeroed.
+ *      swd_project: proj [D, n] (direction-major), proj[d, j] = sum_k dirs[k, d] ((v_jk - mu_c(k)) r_c(k)), dirs [147, D]; the
+ *      mean is subtracted from the gathered value before the multiplication, the sum is a k-ordered fp32 fmaf chain
+ *      (v_mfma_f32_32x32x2_f32).  N 3 S S and N P below 2^31.
+ *      swd_distance: out[0] = mean_i |a[i] - b[i]| over `count` values (two sorted projection sets; the sort is the caller's):
+ *      the difference in fp32, the sum in fp64 in a fixed order, one rounding to fp32.  `workspace`:
+ *      locate_swd_distance_workspace_bytes() bytes, 8-byte aligned. ---- */
+int locate_pyr_down(const float* x, int planes, int S, float* out, void* stream);
+int locate_pyr_residual(const float* x, const float* coarse, int planes, int S, float* out, void* stream);
+size_t locate_swd_stats_workspace_bytes(void);
+int locate_swd_stats(const float* level, int N, int S, const int32_t* pos, int P, float* stats, void* workspace, void* stream);
+int locate_swd_project(const float* level, int N, int S, const int32_t* pos, int P, const float* dirs, int D, const float* stats,
+                       float* proj, void* stream);
+size_t locate_swd_distance_workspace_bytes(void);
+int locate_swd_distance(const float* a, const float* b, int64_t count, float* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

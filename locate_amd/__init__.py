@@ -12,6 +12,8 @@ from .checkpoint import load_checkpoint, save_checkpoint  # noqa: F401
 from .train import TrainLoop, TrainStep  # noqa: F401
 from .data import DeviceImageStore, InputPipeline, draw_params, prepare_folder  # noqa: F401
 from .monitor import LossHistory, Sampler, image_grid  # noqa: F401
+from .metric import (SlicedWasserstein, descriptor_stats, laplacian_pyramid, project_descriptors, pyramid_levels,  # noqa: F401
+                     sorted_distance)
 
 
 def __getattr__(name):

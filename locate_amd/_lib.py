@@ -130,6 +130,13 @@ PROTOTYPES = {
     "locate_image_range_workspace_bytes": (c_sz, []),
     "locate_image_range": (c_i, [c_p, c_i64, c_p, c_p, c_p]),
     "locate_image_grid": (c_i, [c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_f, c_p, c_p, c_p]),
+    "locate_pyr_down": (c_i, [c_p, c_i, c_i, c_p, c_p]),
+    "locate_pyr_residual": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
+    "locate_swd_stats_workspace_bytes": (c_sz, []),
+    "locate_swd_stats": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p]),
+    "locate_swd_project": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
+    "locate_swd_distance_workspace_bytes": (c_sz, []),
+    "locate_swd_distance": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p]),
 }
 
 
@@ -139,7 +146,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 10
+EXPECTED_ABI = 11
 
 
 _lib = None

@@ -4,6 +4,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
 
     python -m locate_amd.run --store FILE.npy --image-size S --batch B --out DIR [--epochs N] [--max-iterations N]
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
+                             [--swd-images 0]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -14,8 +15,11 @@ Differences from the reference, all additions:
   * every iteration that steps the optimizers is recorded for the loss curves (a record is two small launches and no host read);
     the reference appends only the values it prints.  The progress line at `print_every` is the only place a loss is read on
     the host;
-  * the per-iteration latents come from a generator of the trainer's own, so that its state can be saved."""
+  * the per-iteration latents come from a generator of the trainer's own, so that its state can be saved;
+  * `swd=` / `--swd-images N` (off by default): after every epoch the sliced Wasserstein distance of the generator against N
+    real images (`locate_amd.metric`) is appended to `OUT/error/swd.json`.  The evaluation has no side effect on the training."""
 import argparse
+import json
 import os
 import sys
 import time
@@ -72,11 +76,17 @@ class Trainer:
     every resume).
 
     sampler_options: passed to `Sampler` (nrow, padding, advance_spectral_norm - True, the reference's behaviour, by default).
-    log: a callable taking one line of text (the progress line), or None."""
+    log: a callable taking one line of text (the progress line), or None.
+
+    swd: a `SlicedWasserstein` whose reference is set, or None (the default: nothing below happens).  After each epoch's loss
+    curves and before the state is saved, `swd.evaluate(gen)` runs and {"epoch", "iterations", "levels", "mean"} is appended to the
+    list in `out/error/swd.json` (a resumed run appends to the list it finds).  The evaluation leaves weights, u / v and
+    optimizer states untouched, so the trajectory is that of a run without it.  Under data parallelism only rank 0 should be
+    given one, as with the sampler."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
-                 print_every_function=None, image_interval_function=None, sampler_options=None, log=None):
+                 print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -107,6 +117,7 @@ class Trainer:
         self._seed = int(seed)
         self._latent_rng = None
         self.log = log
+        self.swd = swd
         self.epoch, self.sub, self.i, self.iterations = 0, 0, 0, 0
         self._runner = None
         self.written = []
@@ -194,6 +205,21 @@ class Trainer:
         os.makedirs(os.path.dirname(path), exist_ok=True)
         self.written.append(self.sampler.save(path))
 
+    def _measure(self, e):
+        """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
+        value = self.swd.evaluate(self.gen)
+        path = os.path.join(self.out, "error", "swd.json")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        records = []
+        if os.path.exists(path):
+            with open(path) as f:
+                records = json.load(f)
+        records.append({"epoch": e + 1, "iterations": self.iterations, "levels": value["levels"], "mean": value["mean"]})
+        with open(path + ".tmp", "w") as f:
+            json.dump(records, f)
+        os.replace(path + ".tmp", path)
+        return path
+
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
         returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
@@ -224,6 +250,8 @@ class Trainer:
                 self.sub, self.i = self.sub + 1, 0
             self.written += self.history.save(os.path.join(self.out, "error"), e + 1)          # :226-234
             self.history = LossHistory(self.history.mean_window)          # dhist / ghist start empty in every epoch (:107-108)
+            if self.swd is not None:
+                self.written.append(self._measure(e))
             self.epoch, self.sub = e + 1, 0
             self.written += self.save_state()          # :235-236
         return self.iterations
@@ -245,6 +273,9 @@ def main(argv=None):
     ap.add_argument("--resume", action="store_true", help="continue from the files in --out")
     ap.add_argument("--keep-spectral-norm", action="store_true",
                     help="sampling leaves the generator's u / v untouched (the reference's sampling pass advances them)")
+    ap.add_argument("--swd-images", type=int, default=0,
+                    help="after every epoch, the sliced Wasserstein distance of the generator against this many real images "
+                         "(OUT/error/swd.json); 0: off")
     args = ap.parse_args(argv)
 
     from . import DeviceImageStore, Discriminator, Generator, InputPipeline, NetConfig, TrainStep, get_model
@@ -265,8 +296,13 @@ def main(argv=None):
         sys.stdout.write("\r" + line)
         sys.stdout.flush()
 
+    swd = None
+    if args.swd_images > 0:
+        from .metric import SlicedWasserstein
+        swd = SlicedWasserstein(args.image_size, images=args.swd_images, seed=args.seed, chunk=min(64, args.swd_images), device=dev)
+        swd.reference_from_pipeline(pipeline)
     trainer = Trainer(step, pipeline, args.out, epochs=args.epochs, max_iterations=args.max_iterations, images=args.images,
-                      seed=args.seed, diters=args.diters, graphed=args.graph, log=log,
+                      seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
