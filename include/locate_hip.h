@@ -333,6 +333,18 @@ int locate_nadam_chunk_elems(void);
 int locate_nadam_step(const void* tensors, void* coef, const void* chunks, int n_tensors, int n_chunks, double lr, double beta1,
                       double beta2, double eps, double schedule_decay, double weight_decay, void* stream);
 
+/* ---- exponential moving average of a network's weights (no reference counterpart), every tensor in one launch.
+ *      tensors: DEVICE array of {float* avg; const float* src; int64 n; float one_minus_beta} records
+ *      (locate_average_record_bytes() = 32, the float followed by 4 bytes of padding); chunks: DEVICE (tensor index, chunk index)
+ *      int pairs in pieces of locate_average_chunk_elems().  Per element, three fp32 operations, each rounded once and never
+ *      contracted: avg = avg + one_minus_beta * (src - avg).  A record whose one_minus_beta == 1.0f is copied bit for bit
+ *      (avg = src, NaN and Inf payloads included).  avg and src need only 4-byte alignment (16-byte accesses are used where both
+ *      are 16-byte aligned); they must not overlap.  Nothing outside [avg, avg + n) is written.  No allocation, host read or
+ *      synchronisation: legal under stream capture. ---- */
+size_t locate_average_record_bytes(void);
+int locate_average_chunk_elems(void);
+int locate_average_update(const void* tensors, const void* chunks, int n_tensors, int n_chunks, void* stream);
+
 /* ---- loss glue (main.py:149-156,164-169, libs/utils.py:133-134, libs/grad_penalty.py:1-2): values and the
  *      gradients w.r.t. the discriminator outputs ---- */
 int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, float* losses,

@@ -121,6 +121,9 @@ PROTOTYPES = {
     "locate_nadam_tensor_record_bytes": (c_sz, []),
     "locate_nadam_chunk_elems": (c_i, []),
     "locate_nadam_step": (c_i, [c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_p]),
+    "locate_average_record_bytes": (c_sz, []),
+    "locate_average_chunk_elems": (c_i, []),
+    "locate_average_update": (c_i, [c_p, c_p, c_i, c_i, c_p]),
     "locate_d_loss": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "locate_g_loss": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "locate_input_param_record_bytes": (c_sz, []),
@@ -146,7 +149,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 11
+EXPECTED_ABI = 12
 
 
 _lib = None

@@ -4,7 +4,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
 
     python -m locate_amd.run --store FILE.npy --image-size S --batch B --out DIR [--epochs N] [--max-iterations N]
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
-                             [--swd-images 0]
+                             [--swd-images 0] [--ema-half-life 0]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -17,7 +17,14 @@ Differences from the reference, all additions:
     the host;
   * the per-iteration latents come from a generator of the trainer's own, so that its state can be saved;
   * `swd=` / `--swd-images N` (off by default): after every epoch the sliced Wasserstein distance of the generator against N
-    real images (`locate_amd.metric`) is appended to `OUT/error/swd.json`.  The evaluation has no side effect on the training."""
+    real images (`locate_amd.metric`) is appended to `OUT/error/swd.json`.  The evaluation has no side effect on the training;
+  * `average=` / `--ema-half-life IMAGES` (off by default): an exponential moving average of the generator's weights
+    (`locate_amd.average`) whose weight of an old value halves every IMAGES images.  It is updated after every iteration by one
+    launch beside the training step - the trajectory is untouched - and costs one more copy of the generator's parameters (plus
+    its weight panels once it is sampled).  Its spectral-norm u / v are not averaged but copied from the live generator on every
+    update.  Beside each picture `X.png` the average's picture of the same latents is written as `X.ema.png`, the metric's records
+    gain an "average" entry, `OUT/netG_ema.torch` holds the averaged weights in the reference's `state_dict()` layout and
+    `OUT/trainer.torch` the average's whole state, so a resumed run continues it.  Under data parallelism only rank 0 needs one."""
 import argparse
 import json
 import os
@@ -33,6 +40,7 @@ from .train import TrainLoop
 
 MAIN_N = 2 ** 10          # libs/config.py:67
 STATE_FILE = "trainer.torch"
+EMA_FILE = "netG_ema.torch"
 
 
 # ---- the reference's schedule (libs/config.py:19-30, main.py:109-116), per 0-based epoch e ----
@@ -82,11 +90,24 @@ class Trainer:
     curves and before the state is saved, `swd.evaluate(gen)` runs and {"epoch", "iterations", "levels", "mean"} is appended to the
     list in `out/error/swd.json` (a resumed run appends to the list it finds).  The evaluation leaves weights, u / v and
     optimizer states untouched, so the trajectory is that of a run without it.  Under data parallelism only rank 0 should be
-    given one, as with the sampler."""
+    given one, as with the sampler.
+
+    average: an `AveragedGenerator` over step.gen, or None (the default: nothing below happens, and every file, record and key is
+    what it is without this argument).  `average.update()` runs after every iteration of this loop, on the stream the iteration
+    was issued on: ONE update per trainer iteration - the two warm-up iterations that `GraphedTrainStep` runs when it is built
+    (above) belong to the iteration that builds it and are followed by one update, not three.  A second `Sampler` over
+    `average.generator` shares the first one's fixed latents and never advances u / v: beside every picture `X.png` it writes
+    `X.ema.png`.  The metric is evaluated for both generators; its record gains "average": {"levels", "mean"}.  save_state() also
+    writes `netG_ema.torch` - the averaged weights in the reference's `state_dict()` layout, which load into the reference's
+    Generator for inference - and puts `average.state_dict()` under "average" in trainer.torch; resume() restores it, so a resumed
+    run's average continues the uninterrupted run's bit for bit (eager; a graphed run's two warm-up iterations per resume move
+    the weights it follows).  Resuming from a trainer.torch without an average starts it from the resumed weights.  Under data
+    parallelism only rank 0 needs one: the weights are equal on every rank."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
-                 print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None):
+                 print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
+                 average=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -118,6 +139,8 @@ class Trainer:
         self._latent_rng = None
         self.log = log
         self.swd = swd
+        self.average = average
+        self._ema_sampler = None
         self.epoch, self.sub, self.i, self.iterations = 0, 0, 0, 0
         self._runner = None
         self.written = []
@@ -128,6 +151,14 @@ class Trainer:
         if self._sampler is None:
             self._sampler = Sampler(self.gen, **self._sampler_args)
         return self._sampler
+
+    @property
+    def ema_sampler(self):
+        """the averaged generator's sampler: the first one's latents (the same tensor), u / v never advanced"""
+        if self._ema_sampler is None:
+            options = {k: v for k, v in self._sampler_args.items() if k in ("nrow", "padding")}
+            self._ema_sampler = Sampler(self.average.generator, fixed_noise=self.sampler.fixed_noise, advance_spectral_norm=False, **options)
+        return self._ema_sampler
 
     @property
     def _latent_gen(self):
@@ -152,6 +183,12 @@ class Trainer:
         state = {"epoch": self.epoch, "sub": self.sub, "i": self.i, "iterations": self.iterations,
                  "pipeline": self.pipeline.state_dict(), "fixed_noise": self.sampler.fixed_noise.detach().cpu(),
                  "latent_state": self._latent_gen.get_state(), "history": self.history.state_dict()}
+        if self.average is not None:
+            ema = os.path.join(self.out, EMA_FILE)
+            torch.save(self.average.generator_state_dict(), ema + ".tmp")
+            os.replace(ema + ".tmp", ema)
+            files.append(ema)
+            state["average"] = self.average.state_dict()
         path = os.path.join(self.out, STATE_FILE)
         torch.save(state, path + ".tmp")
         os.replace(path + ".tmp", path)
@@ -169,6 +206,11 @@ class Trainer:
         self.sampler.fixed_noise.copy_(noise)
         self._latent_gen.set_state(state["latent_state"])
         self.history.load_state_dict(state["history"])
+        if self.average is not None:
+            if "average" in state:
+                self.average.load_state_dict(state["average"])
+            else:
+                self.average.reset()          # a run that had none: the average starts from the resumed weights
         return self
 
     # ---- the loop -------------------------------------------------------------------------------------------
@@ -204,6 +246,8 @@ class Trainer:
         path = self.picture_path(e, sub, i)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         self.written.append(self.sampler.save(path))
+        if self.average is not None:
+            self.written.append(self.ema_sampler.save(path[:-len(".png")] + ".ema.png"))
 
     def _measure(self, e):
         """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
@@ -215,6 +259,9 @@ class Trainer:
             with open(path) as f:
                 records = json.load(f)
         records.append({"epoch": e + 1, "iterations": self.iterations, "levels": value["levels"], "mean": value["mean"]})
+        if self.average is not None:
+            value = self.swd.evaluate(self.average.generator)
+            records[-1]["average"] = {"levels": value["levels"], "mean": value["mean"]}
         with open(path + ".tmp", "w") as f:
             json.dump(records, f)
         os.replace(path + ".tmp", path)
@@ -237,6 +284,8 @@ class Trainer:
                         self.written += self.save_state()
                         return self.iterations
                     out = self._iteration()
+                    if self.average is not None:
+                        self.average.update()          # one launch on this stream, behind the iteration's last write
                     self.i += 1
                     self.iterations += 1
                     i = self.i
@@ -276,6 +325,9 @@ def main(argv=None):
     ap.add_argument("--swd-images", type=int, default=0,
                     help="after every epoch, the sliced Wasserstein distance of the generator against this many real images "
                          "(OUT/error/swd.json); 0: off")
+    ap.add_argument("--ema-half-life", type=float, default=0.0, metavar="IMAGES",
+                    help="keep an exponential moving average of the generator's weights whose weight of an old value halves every "
+                         "IMAGES images: X.ema.png beside every picture, OUT/netG_ema.torch, an \"average\" entry in swd.json; 0: off")
     args = ap.parse_args(argv)
 
     from . import DeviceImageStore, Discriminator, Generator, InputPipeline, NetConfig, TrainStep, get_model
@@ -301,8 +353,12 @@ def main(argv=None):
         from .metric import SlicedWasserstein
         swd = SlicedWasserstein(args.image_size, images=args.swd_images, seed=args.seed, chunk=min(64, args.swd_images), device=dev)
         swd.reference_from_pipeline(pipeline)
+    average = None
+    if args.ema_half_life > 0:
+        from .average import AveragedGenerator
+        average = AveragedGenerator(gen, half_life_images=args.ema_half_life, batch=args.batch)
     trainer = Trainer(step, pipeline, args.out, epochs=args.epochs, max_iterations=args.max_iterations, images=args.images,
-                      seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd,
+                      seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
