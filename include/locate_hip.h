@@ -345,6 +345,32 @@ size_t locate_average_record_bytes(void);
 int locate_average_chunk_elems(void);
 int locate_average_update(const void* tensors, const void* chunks, int n_tensors, int n_chunks, void* stream);
 
+/* ---- per-tensor statistics with a non-finite guard (no reference counterpart), every tensor of a table in one pass over memory.
+ *      tensors: DEVICE array of {const float* x; int64 n; int32 first_chunk; int32 pad} records
+ *      (locate_stats_tensor_record_bytes() = 24); chunks: DEVICE (tensor index, chunk index) int pairs in pieces of
+ *      locate_stats_chunk_elems(), a tensor's chunks consecutive and in ascending order, its chunk 0 at position first_chunk of
+ *      the array.  records: n_tensors records {double sumsq; float absmax; uint32 nonfinite} (locate_stats_record_bytes() = 16),
+ *      8-byte aligned:
+ *        sumsq      sum of (double) x * (double) x over the FINITE elements (each square is exact; only the additions round:
+ *                   within n 2^-52 relative of the exact sum);
+ *        absmax     largest |x| among the finite elements, exact, denormals included; 0 if there is none;
+ *        nonfinite  elements whose exponent field is all ones (NaN of either sign and any payload, +-Inf), modulo 2^32.
+ *      summary: {uint32 total of nonfinite over the table; int32 index of the first tensor in table order that has one, or -1}.
+ *      workspace: locate_stats_workspace_bytes(n_chunks) bytes, 8-byte aligned, need not be zeroed.
+ *      A tensor's record depends only on its contents and n - not on the table around it, its position, its alignment (x needs
+ *      4 bytes; 16-byte loads are used where a chunk is 16-byte aligned) or the grid: two calls give the same bits.  Two launches
+ *      (a partial per chunk, then one block per tensor adds its partials in a fixed order); no floating-point atomics.  Only
+ *      records, summary and workspace are written.  A table entry that is out of range or inconsistent is skipped: its record is
+ *      then unspecified, and nothing outside the three outputs is written.  No allocation, host read or synchronisation: legal
+ *      under stream capture.  At most locate_stats_max_blocks() blocks stride over the chunk table. ---- */
+size_t locate_stats_tensor_record_bytes(void);
+size_t locate_stats_record_bytes(void);
+int locate_stats_chunk_elems(void);
+int locate_stats_max_blocks(void);
+size_t locate_stats_workspace_bytes(int n_chunks);
+int locate_stats_reduce(const void* tensors, const void* chunks, int n_tensors, int n_chunks, void* records, void* summary,
+                        void* workspace, void* stream);
+
 /* ---- loss glue (main.py:149-156,164-169, libs/utils.py:133-134, libs/grad_penalty.py:1-2): values and the
  *      gradients w.r.t. the discriminator outputs ---- */
 int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, float* losses,

@@ -124,6 +124,12 @@ PROTOTYPES = {
     "locate_average_record_bytes": (c_sz, []),
     "locate_average_chunk_elems": (c_i, []),
     "locate_average_update": (c_i, [c_p, c_p, c_i, c_i, c_p]),
+    "locate_stats_tensor_record_bytes": (c_sz, []),
+    "locate_stats_record_bytes": (c_sz, []),
+    "locate_stats_chunk_elems": (c_i, []),
+    "locate_stats_max_blocks": (c_i, []),
+    "locate_stats_workspace_bytes": (c_sz, [c_i]),
+    "locate_stats_reduce": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
     "locate_d_loss": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "locate_g_loss": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "locate_input_param_record_bytes": (c_sz, []),

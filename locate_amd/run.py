@@ -4,7 +4,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
 
     python -m locate_amd.run --store FILE.npy --image-size S --batch B --out DIR [--epochs N] [--max-iterations N]
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
-                             [--swd-images 0] [--ema-half-life 0]
+                             [--swd-images 0] [--ema-half-life 0] [--stats-every 0]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -24,7 +24,12 @@ Differences from the reference, all additions:
     its weight panels once it is sampled).  Its spectral-norm u / v are not averaged but copied from the live generator on every
     update.  Beside each picture `X.png` the average's picture of the same latents is written as `X.ema.png`, the metric's records
     gain an "average" entry, `OUT/netG_ema.torch` holds the averaged weights in the reference's `state_dict()` layout and
-    `OUT/trainer.torch` the average's whole state, so a resumed run continues it.  Under data parallelism only rank 0 needs one."""
+    `OUT/trainer.torch` the average's whole state, so a resumed run continues it.  Under data parallelism only rank 0 needs one;
+  * `stats=` / `--stats-every N` (off by default): after every N-th iteration one record of per-tensor statistics - sum of
+    squares, largest magnitude, number of non-finite elements of every weight and every gradient of both networks
+    (`locate_amd.stats`) - is taken by a launch beside the training step; `OUT/error/{epoch}-stats.npz` holds an epoch's records.
+    The records are checked wherever the losses are read and immediately before every save: a run that holds a NaN or an Inf
+    stops with `NonFiniteError`, writes `OUT/error/nonfinite.json` and leaves the files of the last good save as they are."""
 import argparse
 import json
 import os
@@ -102,12 +107,24 @@ class Trainer:
     Generator for inference - and puts `average.state_dict()` under "average" in trainer.torch; resume() restores it, so a resumed
     run's average continues the uninterrupted run's bit for bit (eager; a graphed run's two warm-up iterations per resume move
     the weights it follows).  Resuming from a trainer.torch without an average starts it from the resumed weights.  Under data
-    parallelism only rank 0 needs one: the weights are equal on every rank."""
+    parallelism only rank 0 needs one: the weights are equal on every rank.
+
+    stats: a `RunStatistics` over step.gen and step.dis, or None (the default: nothing below happens, and every file, record and key
+    is what it is without this argument).  `stats.record(iterations)` follows every `stats_every`-th iteration of this loop
+    (counted across resumes; 0: only the records below), after `average.update()` and on the same stream: it reads the post-step
+    weights and the gradients the optimizer steps consumed, and writes nothing the training reads.  `stats.check()` runs where
+    this loop reads from the device anyway - with the progress line - and IMMEDIATELY BEFORE every save_state(), at the end of
+    an epoch and when `max_iterations` stops the run; if the last iteration has no record, one is taken first, so no state is
+    saved unchecked.  On `NonFiniteError` the trainer writes `out/error/nonfinite.json` - {"iteration", "epoch" (1-based),
+    "tensors": [[name, count], ...]} - does NOT save the state, so the files of the last good save stay byte for byte, and
+    re-raises.  `out/error/{e+1}-stats.npz` (`RunStatistics.save`) is written beside the loss curves and holds the records of that
+    epoch taken by this call of run(); the records start empty in every epoch, like the curves.  Under data parallelism only
+    rank 0 needs one: the weights, and the gradients after the exchange, are equal on every rank."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
-                 average=None):
+                 average=None, stats=None, stats_every=16):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -141,6 +158,9 @@ class Trainer:
         self.swd = swd
         self.average = average
         self._ema_sampler = None
+        if int(stats_every) < 0:
+            raise ValueError("stats_every must be >= 0, got %r" % (stats_every,))
+        self.stats, self.stats_every = stats, int(stats_every)
         self.epoch, self.sub, self.i, self.iterations = 0, 0, 0, 0
         self._runner = None
         self.written = []
@@ -213,6 +233,23 @@ class Trainer:
                 self.average.reset()          # a run that had none: the average starts from the resumed weights
         return self
 
+    def _check_stats(self, before_save=False):
+        """stats.check(); before a save, preceded by a record of the state that is about to be saved if it has none.  A run that
+        holds a non-finite value leaves out/error/nonfinite.json and raises."""
+        from .stats import NonFiniteError
+        if before_save and self.iterations > 0 and self.stats.last_iteration != self.iterations:
+            self.stats.record(self.iterations)
+        try:
+            self.stats.check()
+        except NonFiniteError as err:
+            path = os.path.join(self.out, "error", "nonfinite.json")
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+            with open(path + ".tmp", "w") as f:
+                json.dump({"iteration": err.iteration, "epoch": self.epoch + 1, "tensors": [list(t) for t in err.tensors]}, f)
+            os.replace(path + ".tmp", path)
+            self.written.append(path)
+            raise
+
     # ---- the loop -------------------------------------------------------------------------------------------
     def _iteration(self):
         latent_shape = (self.batch, self.gen.g_in)
@@ -234,6 +271,8 @@ class Trainer:
     def _progress(self, e, sub, i, first, subepochs, batches, started):
         """first: the position this call of run() entered the sub-pass at (not 0 after a resume): the rate counts from there"""
         pairs = self.history.flush()          # the one host read of the losses
+        if self.stats is not None:
+            self._check_stats()
         if self.log is None or not (self.history.d and self.history.g):
             return
         rate = (i - first) / max(time.time() - started, 1e-9)
@@ -281,6 +320,8 @@ class Trainer:
                 self.loop.i = self.i          # i restarts at 1 in every sub-pass (main.py:140)
                 while self.i < batches:
                     if self.max_iterations is not None and self.iterations >= self.max_iterations:
+                        if self.stats is not None:
+                            self._check_stats(before_save=True)
                         self.written += self.save_state()
                         return self.iterations
                     out = self._iteration()
@@ -288,6 +329,8 @@ class Trainer:
                         self.average.update()          # one launch on this stream, behind the iteration's last write
                     self.i += 1
                     self.iterations += 1
+                    if self.stats is not None and self.stats_every and self.iterations % self.stats_every == 0:
+                        self.stats.record(self.iterations)          # two launches on this stream, no host read
                     i = self.i
                     if i % miniter == 0:          # main.py:158
                         self.history.record(out)
@@ -297,11 +340,18 @@ class Trainer:
                             self._picture(e, self.sub, i)
                 self._picture(e, self.sub, None)          # :213-225
                 self.sub, self.i = self.sub + 1, 0
+            if self.stats is not None:
+                self._check_stats(before_save=True)          # the epoch's last record, in front of the files that hold it
             self.written += self.history.save(os.path.join(self.out, "error"), e + 1)          # :226-234
             self.history = LossHistory(self.history.mean_window)          # dhist / ghist start empty in every epoch (:107-108)
+            if self.stats is not None:
+                self.written += self.stats.save(os.path.join(self.out, "error"), e + 1)
+                self.stats.clear()
             if self.swd is not None:
                 self.written.append(self._measure(e))
             self.epoch, self.sub = e + 1, 0
+            if self.stats is not None:
+                self._check_stats(before_save=True)
             self.written += self.save_state()          # :235-236
         return self.iterations
 
@@ -328,7 +378,12 @@ def main(argv=None):
     ap.add_argument("--ema-half-life", type=float, default=0.0, metavar="IMAGES",
                     help="keep an exponential moving average of the generator's weights whose weight of an old value halves every "
                          "IMAGES images: X.ema.png beside every picture, OUT/netG_ema.torch, an \"average\" entry in swd.json; 0: off")
+    ap.add_argument("--stats-every", type=int, default=0, metavar="N",
+                    help="after every N-th iteration, record per-tensor weight and gradient statistics (OUT/error/EPOCH-stats.npz) "
+                         "and stop with an error, before anything is saved, once a weight or gradient is NaN or Inf; 0: off")
     args = ap.parse_args(argv)
+    if args.stats_every < 0:
+        ap.error("--stats-every must be >= 0")
 
     from . import DeviceImageStore, Discriminator, Generator, InputPipeline, NetConfig, TrainStep, get_model
     from ._lib import require_gpu
@@ -357,8 +412,13 @@ def main(argv=None):
     if args.ema_half_life > 0:
         from .average import AveragedGenerator
         average = AveragedGenerator(gen, half_life_images=args.ema_half_life, batch=args.batch)
+    stats = None
+    if args.stats_every > 0:
+        from .stats import RunStatistics
+        stats = RunStatistics(gen, dis)
     trainer = Trainer(step, pipeline, args.out, epochs=args.epochs, max_iterations=args.max_iterations, images=args.images,
-                      seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average,
+                      seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average, stats=stats,
+                      stats_every=args.stats_every if stats is not None else 16,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
