@@ -371,6 +371,36 @@ size_t locate_stats_workspace_bytes(int n_chunks);
 int locate_stats_reduce(const void* tensors, const void* chunks, int n_tensors, int n_chunks, void* records, void* summary,
                         void* workspace, void* stream);
 
+/* ---- guarded Nadam step (no reference counterpart): locate_nadam_step behind a verdict taken on the device from the gradients.
+ *      grads: DEVICE array of n_grads {const float* g; int64 n} records (locate_guard_tensor_record_bytes() = 16) over EVERY gradient
+ *      of the optimizer, all parameter groups together; grad_chunks: DEVICE (tensor index, chunk index) int pairs in pieces of
+ *      locate_guard_chunk_elems(); workspace: locate_guard_workspace_bytes(n_grad_chunks) bytes, 8-byte aligned, need not be zeroed.
+ *      verdict: locate_guard_verdict_bytes() = 64 bytes, 8-byte aligned, zeroed ONCE by the caller, read and written:
+ *        {double norm; uint64 nonfinite; float scale; int32 skip; int64 steps, skipped, clipped, consecutive_skips; double sumsq}
+ *        sumsq      sum of (double) g * (double) g over the FINITE gradient elements (within n 2^-52 relative of the exact sum),
+ *                   norm = sqrt(sumsq); nonfinite: elements whose exponent field is all ones;
+ *        skip       skip_nonfinite != 0 && nonfinite > 0;
+ *        scale      (float)(max_norm / norm), the division in double, when max_norm > 0 && norm > max_norm && !skip; else 1.0f
+ *                   (torch's clip_grad_norm_ divides by norm + 1e-6 instead);
+ *        steps counts the verdicts, skipped / clipped those with skip / a scale below 1, consecutive_skips the skipped steps since
+ *        the last step that was taken.
+ *      n_grads > 0: a reduce launch (at most locate_guard_max_blocks() blocks stride over the chunk table; 16-byte loads between a
+ *      scalar head and tail, so g needs 4-byte alignment only) and a one-block verdict launch run first.  n_grads == 0 (then grads,
+ *      grad_chunks, workspace NULL and n_grad_chunks 0): the verdict the record holds is applied - the later parameter groups of a step.
+ *      Then, for the ONE parameter group given as in locate_nadam_step: skip == 0: the Nadam step on g * scale (one fp32 multiply,
+ *      rounded on its own; weight decay added after it); scale == 1.0f gives locate_nadam_step's bits.  skip == 1: p, m, v, sched keep
+ *      every bit; the absmax words are cleared and refilled with max |p|.  g is never written.  No floating-point atomics, no
+ *      allocation, host read or synchronisation: legal under stream capture, where the decision is taken at every replay. ---- */
+size_t locate_guard_tensor_record_bytes(void);
+size_t locate_guard_verdict_bytes(void);
+int locate_guard_chunk_elems(void);
+int locate_guard_max_blocks(void);
+size_t locate_guard_workspace_bytes(int n_chunks);
+int locate_guarded_nadam_step(const void* grads, const void* grad_chunks, int n_grads, int n_grad_chunks, void* workspace, void* verdict,
+                              double max_norm, int skip_nonfinite, const void* tensors, void* coef, const void* chunks, int n_tensors,
+                              int n_chunks, double lr, double beta1, double beta2, double eps, double schedule_decay, double weight_decay,
+                              void* stream);
+
 /* ---- loss glue (main.py:149-156,164-169, libs/utils.py:133-134, libs/grad_penalty.py:1-2): values and the
  *      gradients w.r.t. the discriminator outputs ---- */
 int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, float* losses,

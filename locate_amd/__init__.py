@@ -16,6 +16,7 @@ from .metric import (SlicedWasserstein, descriptor_stats, laplacian_pyramid, pro
                      sorted_distance)
 from .average import AveragedGenerator, average_weight  # noqa: F401
 from .stats import NonFiniteError, RunStatistics, tensor_statistics  # noqa: F401
+from .guard import GuardedNadam, GuardExhausted  # noqa: F401
 
 
 def __getattr__(name):

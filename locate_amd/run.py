@@ -5,6 +5,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
     python -m locate_amd.run --store FILE.npy --image-size S --batch B --out DIR [--epochs N] [--max-iterations N]
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
                              [--swd-images 0] [--ema-half-life 0] [--stats-every 0]
+                             [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -29,7 +30,12 @@ Differences from the reference, all additions:
     squares, largest magnitude, number of non-finite elements of every weight and every gradient of both networks
     (`locate_amd.stats`) - is taken by a launch beside the training step; `OUT/error/{epoch}-stats.npz` holds an epoch's records.
     The records are checked wherever the losses are read and immediately before every save: a run that holds a NaN or an Inf
-    stops with `NonFiniteError`, writes `OUT/error/nonfinite.json` and leaves the files of the last good save as they are."""
+    stops with `NonFiniteError`, writes `OUT/error/nonfinite.json` and leaves the files of the last good save as they are;
+  * `--clip-grad-norm X` / `--no-skip-nonfinite` (without either, nothing below happens): both networks are stepped by
+    `GuardedNadam` (`locate_amd.guard`) instead of `Nadam`: a step whose gradients hold a NaN or an Inf is skipped on the device
+    (unless `--no-skip-nonfinite`), and with X > 0 the gradients are scaled down to the global norm X.  `OUT/error/{epoch}-guard.json`
+    holds both optimizers' counters, `OUT/trainer.torch` carries them through `--resume`, and a run whose optimizer has skipped
+    `--max-consecutive-skips` steps in a row stops with `GuardExhausted` like a run that holds a NaN does."""
 import argparse
 import json
 import os
@@ -119,12 +125,22 @@ class Trainer:
     "tensors": [[name, count], ...]} - does NOT save the state, so the files of the last good save stay byte for byte, and
     re-raises.  `out/error/{e+1}-stats.npz` (`RunStatistics.save`) is written beside the loss curves and holds the records of that
     epoch taken by this call of run(); the records start empty in every epoch, like the curves.  Under data parallelism only
-    rank 0 needs one: the weights, and the gradients after the exchange, are equal on every rank."""
+    rank 0 needs one: the weights, and the gradients after the exchange, are equal on every rank.
+
+    Guarded optimizers: where step.gen_opt or step.dis_opt is a `GuardedNadam` (anything with `counters()`; with plain `Nadam`s
+    nothing below happens, and every file, record and key is what it is today), its counters are read where this loop reads from
+    the device anyway - with the progress line - and before every save_state().  An optimizer whose `consecutive_skips` has reached
+    `max_consecutive_skips` (default 16, the reference's progress interval at batch 64) would skip every further step too - its
+    gradients are non-finite whatever the batch, usually because a weight is: the trainer writes `out/error/nonfinite.json` -
+    {"iteration", "epoch", "tensors": [], "guard": {"network", "counters"}} - does NOT save the state and raises
+    `GuardExhausted(.iteration, .network)`.  Once per epoch `out/error/{e+1}-guard.json` - {"G": counters, "D": counters}, the
+    guarded ones only - is written beside the loss curves; save_state() puts the counters under "guard" in trainer.torch and
+    resume() restores them."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
-                 average=None, stats=None, stats_every=16):
+                 average=None, stats=None, stats_every=16, max_consecutive_skips=16):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -161,6 +177,9 @@ class Trainer:
         if int(stats_every) < 0:
             raise ValueError("stats_every must be >= 0, got %r" % (stats_every,))
         self.stats, self.stats_every = stats, int(stats_every)
+        if int(max_consecutive_skips) < 1:
+            raise ValueError("max_consecutive_skips must be >= 1, got %r" % (max_consecutive_skips,))
+        self.max_consecutive_skips = int(max_consecutive_skips)
         self.epoch, self.sub, self.i, self.iterations = 0, 0, 0, 0
         self._runner = None
         self.written = []
@@ -209,6 +228,8 @@ class Trainer:
             os.replace(ema + ".tmp", ema)
             files.append(ema)
             state["average"] = self.average.state_dict()
+        if self._guards():
+            state["guard"] = {tag: opt.counters_state() for tag, opt in self._guards()}
         path = os.path.join(self.out, STATE_FILE)
         torch.save(state, path + ".tmp")
         os.replace(path + ".tmp", path)
@@ -231,7 +252,39 @@ class Trainer:
                 self.average.load_state_dict(state["average"])
             else:
                 self.average.reset()          # a run that had none: the average starts from the resumed weights
+        for tag, opt in self._guards():
+            if tag in state.get("guard", {}):
+                opt.load_counters_state(state["guard"][tag])
         return self
+
+    def _guards(self):
+        """[("G" | "D", optimizer)] of the optimizers that keep guard counters"""
+        return [(tag, opt) for tag, opt in (("G", self.step.gen_opt), ("D", self.step.dis_opt)) if hasattr(opt, "counters")]
+
+    def _check_guards(self):
+        """One small device read per guarded optimizer; {"G": counters, "D": counters}.  An optimizer that has skipped
+        max_consecutive_skips steps in a row leaves out/error/nonfinite.json and raises."""
+        from .guard import GuardExhausted
+        seen = {tag: opt.counters() for tag, opt in self._guards()}
+        for tag, c in seen.items():
+            if c["consecutive_skips"] >= self.max_consecutive_skips:
+                path = os.path.join(self.out, "error", "nonfinite.json")
+                os.makedirs(os.path.dirname(path), exist_ok=True)
+                with open(path + ".tmp", "w") as f:
+                    json.dump({"iteration": self.iterations, "epoch": self.epoch + 1, "tensors": [],
+                               "guard": {"network": tag, "counters": c}}, f)
+                os.replace(path + ".tmp", path)
+                self.written.append(path)
+                raise GuardExhausted(self.iterations, tag, c["consecutive_skips"])
+        return seen
+
+    def _save_guards(self, epoch):
+        path = os.path.join(self.out, "error", "%d-guard.json" % epoch)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path + ".tmp", "w") as f:
+            json.dump(self._check_guards(), f)
+        os.replace(path + ".tmp", path)
+        return path
 
     def _check_stats(self, before_save=False):
         """stats.check(); before a save, preceded by a record of the state that is about to be saved if it has none.  A run that
@@ -273,6 +326,8 @@ class Trainer:
         pairs = self.history.flush()          # the one host read of the losses
         if self.stats is not None:
             self._check_stats()
+        if self._guards():
+            self._check_guards()
         if self.log is None or not (self.history.d and self.history.g):
             return
         rate = (i - first) / max(time.time() - started, 1e-9)
@@ -322,6 +377,8 @@ class Trainer:
                     if self.max_iterations is not None and self.iterations >= self.max_iterations:
                         if self.stats is not None:
                             self._check_stats(before_save=True)
+                        if self._guards():
+                            self._check_guards()
                         self.written += self.save_state()
                         return self.iterations
                     out = self._iteration()
@@ -347,6 +404,8 @@ class Trainer:
             if self.stats is not None:
                 self.written += self.stats.save(os.path.join(self.out, "error"), e + 1)
                 self.stats.clear()
+            if self._guards():
+                self.written.append(self._save_guards(e + 1))          # raises, before the save below, if a guard is exhausted
             if self.swd is not None:
                 self.written.append(self._measure(e))
             self.epoch, self.sub = e + 1, 0
@@ -381,9 +440,20 @@ def main(argv=None):
     ap.add_argument("--stats-every", type=int, default=0, metavar="N",
                     help="after every N-th iteration, record per-tensor weight and gradient statistics (OUT/error/EPOCH-stats.npz) "
                          "and stop with an error, before anything is saved, once a weight or gradient is NaN or Inf; 0: off")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="step both networks with GuardedNadam and scale the gradients down to the global L2 norm X where theirs is "
+                         "larger (OUT/error/EPOCH-guard.json holds the counters); 0: guard without clipping")
+    ap.add_argument("--no-skip-nonfinite", action="store_true",
+                    help="step both networks with GuardedNadam but take a step whose gradients hold a NaN or an Inf (it is counted)")
+    ap.add_argument("--max-consecutive-skips", type=int, default=16, metavar="N",
+                    help="stop with an error, before anything is saved, once a guarded optimizer has skipped N steps in a row")
     args = ap.parse_args(argv)
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
+    if args.clip_grad_norm is not None and not (0.0 <= args.clip_grad_norm < float("inf")):
+        ap.error("--clip-grad-norm must be finite and >= 0")
+    if args.max_consecutive_skips < 1:
+        ap.error("--max-consecutive-skips must be >= 1")
 
     from . import DeviceImageStore, Discriminator, Generator, InputPipeline, NetConfig, TrainStep, get_model
     from ._lib import require_gpu
@@ -393,6 +463,12 @@ def main(argv=None):
     torch.manual_seed(cfg.seed)
     gen, gen_opt = get_model(Generator(cfg), cfg.glr, dev, cfg)
     dis, dis_opt = get_model(Discriminator(cfg), cfg.dlr, dev, cfg)
+    if args.clip_grad_norm is not None or args.no_skip_nonfinite:
+        from .guard import GuardedNadam
+        guarded = dict(max_norm=args.clip_grad_norm or 0.0, skip_nonfinite=not args.no_skip_nonfinite)
+        # over get_model's own parameter groups: whatever it sets for Nadam (lr, betas, ...) holds for the guarded step too
+        gen_opt = GuardedNadam(gen_opt.param_groups, **guarded)
+        dis_opt = GuardedNadam(dis_opt.param_groups, **guarded)
     gen.batched_spectral_norm = dis.batched_spectral_norm = True
     step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches)
     pipeline = InputPipeline(DeviceImageStore(args.store, dev), args.image_size, args.batch, seed=args.seed)
@@ -418,7 +494,7 @@ def main(argv=None):
         stats = RunStatistics(gen, dis)
     trainer = Trainer(step, pipeline, args.out, epochs=args.epochs, max_iterations=args.max_iterations, images=args.images,
                       seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average, stats=stats,
-                      stats_every=args.stats_every if stats is not None else 16,
+                      stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
