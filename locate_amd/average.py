@@ -19,6 +19,8 @@ import struct
 import numpy as np
 import torch
 
+from ._tables import chunk_pairs, remember, stage
+
 
 def average_weight(beta=None, half_life_images=None, batch=None):
     """(beta, one_minus_beta) as Python floats.  Exactly one of `beta` (in [0, 1)) or the pair (`half_life_images` > 0, `batch` > 0)
@@ -160,24 +162,10 @@ class AveragedGenerator:
         from ._lib import lib
         L = lib()
         assert L.locate_average_record_bytes() == 32
-        chunk = L.locate_average_chunk_elems()
-        rec = bytearray()
-        chunks = []
-        n_t = 0
-        for a, s, w in self._pairs:
-            if a.numel() == 0:
-                continue
-            rec += struct.pack("<QQqf4x", a.data_ptr(), s.data_ptr(), a.numel(), w)
-            chunks.extend((n_t, c) for c in range((a.numel() + chunk - 1) // chunk))
-            n_t += 1
-        dev = self._pairs[0][0].device
-        # pinned staging + async copies, as in Nadam._table; the host buffers are kept alive with the table
-        t_host = torch.frombuffer(rec, dtype=torch.uint8).clone().pin_memory()
-        c_host = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).pin_memory()
-        tab = (t_host.to(dev, non_blocking=True), c_host.to(dev, non_blocking=True), n_t, len(chunks), t_host, c_host)
-        self._tables.clear()
-        self._tables[key] = tab
-        return tab
+        live = [(a, s, w) for a, s, w in self._pairs if a.numel() > 0]
+        rec = b"".join(struct.pack("<QQqf4x", a.data_ptr(), s.data_ptr(), a.numel(), w) for a, s, w in live)
+        pairs, _ = chunk_pairs([a.numel() for a, _, _ in live], L.locate_average_chunk_elems())
+        return remember(self._tables, key, stage(rec, pairs, len(live), self._pairs[0][0].device), 0)          # one table at a time
 
     def update(self):
         """One step of the average towards the live weights; u / v and buffers copied.  One launch on

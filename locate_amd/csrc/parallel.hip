@@ -1,8 +1,8 @@
 // Gradient bucket pack / unpack for the data-parallel exchange (locate_amd/parallel.py): the ~140 gradient tensors of a
 // network are copied into a few flat buckets before the RCCL all-reduce and back (scaled by 1 / world when the collective
-// sums instead of averaging) afterwards - one launch per bucket and direction, driven by a device table, instead of an
-// ATen multi-tensor copy.  The reference has no counterpart (single process, single device: libs/config.py:10-11).
-#include "common.h"
+// sums instead of averaging) afterwards - one launch per bucket and direction, driven by a chunk table (multitensor.h), instead
+// of an ATen multi-tensor copy.  The reference has no counterpart (single process, single device: libs/config.py:10-11).
+#include "multitensor.h"
 
 struct CopyTensor {
     float* grad;        // the parameter's gradient
@@ -10,21 +10,19 @@ struct CopyTensor {
     long long n;
 };
 
-#define MC_CHUNK 4096
-
 // direction 0: flat <- grad (pack);  1: grad <- flat * scale (unpack)
 __global__ void __launch_bounds__(256) multi_copy_kernel(const CopyTensor* __restrict__ tensors, const int2* __restrict__ chunks,
                                                          int direction, float scale) {
-    const int2 ch = chunks[blockIdx.x];
-    const CopyTensor T = tensors[ch.x];
-    const long long begin = (long long)ch.y * MC_CHUNK;
-    long long end = begin + MC_CHUNK;
-    if (end > T.n) end = T.n;
+    CopyTensor T;
+    long long begin;
+    int len;
+    if (!mt_decode(tensors, MT_ANY_TENSOR, chunks[blockIdx.x], T, begin, len)) return;
+    const long long end = begin + len;
     const float* __restrict__ src = direction == 0 ? T.grad : T.flat;
     float* __restrict__ dst = direction == 0 ? T.flat : T.grad;
     const bool vec = ((reinterpret_cast<uintptr_t>(src + begin) | reinterpret_cast<uintptr_t>(dst + begin)) & 15) == 0;
     if (vec) {
-        const long long n4 = (end - begin) >> 2;
+        const long long n4 = len >> 2;
         const float4* s4 = reinterpret_cast<const float4*>(src + begin);
         float4* d4 = reinterpret_cast<float4*>(dst + begin);
         for (long long i = threadIdx.x; i < n4; i += blockDim.x) {
@@ -39,7 +37,7 @@ __global__ void __launch_bounds__(256) multi_copy_kernel(const CopyTensor* __res
 }
 
 LOCATE_API size_t locate_multi_copy_record_bytes(void) { return sizeof(CopyTensor); }
-LOCATE_API int locate_multi_copy_chunk_elems(void) { return MC_CHUNK; }
+LOCATE_API int locate_multi_copy_chunk_elems(void) { return MT_CHUNK; }
 
 // tensors: DEVICE array of records {grad, flat, n}; chunks: DEVICE array of n_chunks (tensor index, chunk index) int pairs
 // covering every tensor in locate_multi_copy_chunk_elems() pieces.  direction 0 packs (flat <- grad), 1 unpacks

@@ -5,7 +5,7 @@
 //                        bits & 0x7fffffff - order-preserving for finite values, so exact; denormals count;
 //   nonfinite (uint32)   the elements whose exponent field is all ones: NaN of either sign and any payload, +-Inf;
 // and per call one summary {uint32 total non-finite count, int32 index of the first tensor in table order that has one, or -1}.
-// Driven by a chunk table like the Nadam step (nadam.hip) and the averaged generator (average.hip); like the latter a kernel of
+// Driven by a chunk table (multitensor.h); like the averaged generator (average.hip) a kernel of
 // its own that runs BETWEEN two training iterations and only READS what the step left.  The reference has nothing of the kind.
 //
 // Two launches.  (1) locate_stats_partial_kernel: one block per 4096-element chunk writes that chunk's partial {sumsq, absmax,
@@ -17,14 +17,13 @@
 //
 // A record depends only on its tensor's contents and length - not on the grid, on the tensor's position in the table, on what else
 // the table holds, nor on the tensor's alignment: element 4 (t + 256 k) + j of a chunk always belongs to thread t (k, j < 4),
-// whether it arrived by a 16-byte or a 4-byte load, a thread adds its sixteen squares in index order, a wave combines its lanes
-// by a butterfly, the block its four waves in order, and the combine pass gives partial p to thread p % 256, which adds its
-// partials in ascending order.  Missing elements of a short chunk enter as +0.0, which changes none of the three results.
+// whether it arrived by a 16-byte or a 4-byte load, and every sum has the one order of multitensor.h's reduction.  Missing elements
+// of a short chunk enter as +0.0, which changes none of the three results.
 // No floating-point atomics; the summary is built with integer atomics (an add and a minimum: order-free, so deterministic).
 //
 // A pure bandwidth kernel (4 bytes per element, ~3 operations): 16-byte loads where the chunk is 16-byte aligned, a full chunk's
 // four loads in flight per thread before the first use, at most 2048 blocks (256 CUs x 8) that stride over the chunk table.
-#include "common.h"
+#include "multitensor.h"
 
 struct StatsTensor {
     const float* x;
@@ -33,84 +32,36 @@ struct StatsTensor {
     int pad;
 };
 
-struct StatsRecord {          // a chunk's partial and a tensor's record alike
-    double sumsq;
-    unsigned absmax;          // bit pattern of a non-negative finite fp32
-    unsigned nonfinite;
-};
+typedef MtPartial StatsRecord;          // {sumsq, absmax, nonfinite}: a chunk's partial and a tensor's record alike
 
-#define STATS_CHUNK 4096
-#define STATS_THREADS 256
-#define STATS_WAVES (STATS_THREADS / 64)
-#define STATS_PER_THREAD (STATS_CHUNK / 4 / STATS_THREADS)          // 16-byte words per thread in a full chunk
-#define STATS_MAX_BLOCKS 2048
-
-__device__ __forceinline__ void stats_take(float x, double& s, unsigned& m, unsigned& c) {
-    const unsigned mag = __float_as_uint(x) & 0x7fffffffu;
-    const bool finite = mag < 0x7f800000u;
-    const double d = finite ? (double)x : 0.0;
-    s = fma(d, d, s);          // d * d is exact in fp64: one rounding, that of the addition
-    m = finite && mag > m ? mag : m;
-    c += finite ? 0u : 1u;
-}
-
-// the block's total in thread 0 (other threads: unspecified); `lds` holds STATS_WAVES records
-__device__ __forceinline__ StatsRecord stats_block_reduce(double s, unsigned m, unsigned c, StatsRecord* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o, 64);
-        const unsigned om = (unsigned)__shfl_xor((int)m, o, 64);
-        m = om > m ? om : m;
-        c += (unsigned)__shfl_xor((int)c, o, 64);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();          // lds may still be read from the previous chunk
-    if (lane == 0) {
-        lds[wid].sumsq = s;
-        lds[wid].absmax = m;
-        lds[wid].nonfinite = c;
-    }
-    __syncthreads();
-    StatsRecord r = lds[0];
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < STATS_WAVES; ++w) {
-            r.sumsq += lds[w].sumsq;
-            r.absmax = lds[w].absmax > r.absmax ? lds[w].absmax : r.absmax;
-            r.nonfinite += lds[w].nonfinite;
-        }
-    }
-    return r;
-}
-
-__global__ void __launch_bounds__(STATS_THREADS) locate_stats_partial_kernel(const StatsTensor* __restrict__ tensors,
+__global__ void __launch_bounds__(MT_THREADS) locate_stats_partial_kernel(const StatsTensor* __restrict__ tensors,
                                                                             const int2* __restrict__ chunks, int n_tensors, int n_chunks,
                                                                             StatsRecord* __restrict__ partials, unsigned* __restrict__ summary) {
-    __shared__ StatsRecord lds[STATS_WAVES];
+    __shared__ StatsRecord lds[MT_WAVES];
     if (blockIdx.x == 0 && threadIdx.x == 0) {          // the combine launch behind this one adds into it
         summary[0] = 0u;
         summary[1] = 0xffffffffu;          // -1: no tensor has a non-finite element
     }
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         const int2 ch = chunks[c];
-        if ((unsigned)ch.x >= (unsigned)n_tensors || ch.y < 0) continue;          // a damaged table writes nothing
-        const StatsTensor T = tensors[ch.x];
-        const long long begin = (long long)ch.y * STATS_CHUNK;
-        if (begin >= T.n || (long long)T.first_chunk + ch.y != c) continue;
-        const int len = T.n - begin < STATS_CHUNK ? (int)(T.n - begin) : STATS_CHUNK;
+        StatsTensor T;
+        long long begin;
+        int len;
+        // a damaged table writes nothing
+        if (!mt_decode(tensors, n_tensors, ch, T, begin, len) || (long long)T.first_chunk + ch.y != c) continue;
         const float* x = T.x + begin;
-        float4 v[STATS_PER_THREAD];
-        if ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && len == STATS_CHUNK) {          // a full chunk: every load issued before the first use
+        float4 v[MT_PER_THREAD];
+        if ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && len == MT_CHUNK) {          // a full chunk: every load issued before the first use
             const float4* x4 = reinterpret_cast<const float4*>(x);
 #pragma unroll
-            for (int k = 0; k < STATS_PER_THREAD; ++k) v[k] = x4[threadIdx.x + k * STATS_THREADS];
+            for (int k = 0; k < MT_PER_THREAD; ++k) v[k] = x4[threadIdx.x + k * MT_THREADS];
         } else if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
             const float4* x4 = reinterpret_cast<const float4*>(x);
 #pragma unroll
-            for (int k = 0; k < STATS_PER_THREAD; ++k) {
-                const int e = 4 * (threadIdx.x + k * STATS_THREADS);
+            for (int k = 0; k < MT_PER_THREAD; ++k) {
+                const int e = 4 * (threadIdx.x + k * MT_THREADS);
                 if (e + 4 <= len) {
-                    v[k] = x4[threadIdx.x + k * STATS_THREADS];
+                    v[k] = x4[threadIdx.x + k * MT_THREADS];
                 } else {
                     v[k].x = e < len ? x[e] : 0.0f;
                     v[k].y = e + 1 < len ? x[e + 1] : 0.0f;
@@ -120,8 +71,8 @@ __global__ void __launch_bounds__(STATS_THREADS) locate_stats_partial_kernel(con
             }
         } else {          // a base that is not 16-byte aligned: the same elements per thread through 4-byte loads
 #pragma unroll
-            for (int k = 0; k < STATS_PER_THREAD; ++k) {
-                const int e = 4 * (threadIdx.x + k * STATS_THREADS);
+            for (int k = 0; k < MT_PER_THREAD; ++k) {
+                const int e = 4 * (threadIdx.x + k * MT_THREADS);
                 v[k].x = e < len ? x[e] : 0.0f;
                 v[k].y = e + 1 < len ? x[e + 1] : 0.0f;
                 v[k].z = e + 2 < len ? x[e + 2] : 0.0f;
@@ -131,36 +82,26 @@ __global__ void __launch_bounds__(STATS_THREADS) locate_stats_partial_kernel(con
         double s = 0.0;
         unsigned m = 0u, cnt = 0u;
 #pragma unroll
-        for (int k = 0; k < STATS_PER_THREAD; ++k) {
-            stats_take(v[k].x, s, m, cnt);
-            stats_take(v[k].y, s, m, cnt);
-            stats_take(v[k].z, s, m, cnt);
-            stats_take(v[k].w, s, m, cnt);
-        }
-        const StatsRecord r = stats_block_reduce(s, m, cnt, lds);
+        for (int k = 0; k < MT_PER_THREAD; ++k) mt_take4(v[k], s, m, cnt);
+        const StatsRecord r = mt_block_reduce(s, m, cnt, lds);
         if (threadIdx.x == 0) partials[c] = r;          // c < n_chunks: inside the workspace
     }
 }
 
-__global__ void __launch_bounds__(STATS_THREADS) locate_stats_combine_kernel(const StatsTensor* __restrict__ tensors, int n_tensors, int n_chunks,
+__global__ void __launch_bounds__(MT_THREADS) locate_stats_combine_kernel(const StatsTensor* __restrict__ tensors, int n_tensors, int n_chunks,
                                                                             const StatsRecord* __restrict__ partials,
                                                                             StatsRecord* __restrict__ records, unsigned* __restrict__ summary) {
-    __shared__ StatsRecord lds[STATS_WAVES];
+    __shared__ StatsRecord lds[MT_WAVES];
     for (int t = blockIdx.x; t < n_tensors; t += gridDim.x) {
         const StatsTensor T = tensors[t];
         if (T.n <= 0 || T.first_chunk < 0) continue;          // a damaged table writes nothing
-        const long long nc = (T.n + STATS_CHUNK - 1) / STATS_CHUNK;
+        const long long nc = (T.n + MT_CHUNK - 1) / MT_CHUNK;
         if ((long long)T.first_chunk + nc > n_chunks) continue;
         const StatsRecord* p = partials + T.first_chunk;
         double s = 0.0;
         unsigned m = 0u, cnt = 0u;
-        for (int i = threadIdx.x; i < (int)nc; i += STATS_THREADS) {
-            const StatsRecord q = p[i];
-            s += q.sumsq;
-            m = q.absmax > m ? q.absmax : m;
-            cnt += q.nonfinite;
-        }
-        const StatsRecord r = stats_block_reduce(s, m, cnt, lds);
+        mt_add_partials(p, (int)nc, s, m, cnt);
+        const StatsRecord r = mt_block_reduce(s, m, cnt, lds);
         if (threadIdx.x == 0) {
             records[t] = r;
             if (r.nonfinite) {          // integer atomics: the result does not depend on the order of arrival
@@ -173,8 +114,8 @@ __global__ void __launch_bounds__(STATS_THREADS) locate_stats_combine_kernel(con
 
 LOCATE_API size_t locate_stats_tensor_record_bytes(void) { return sizeof(StatsTensor); }
 LOCATE_API size_t locate_stats_record_bytes(void) { return sizeof(StatsRecord); }
-LOCATE_API int locate_stats_chunk_elems(void) { return STATS_CHUNK; }
-LOCATE_API int locate_stats_max_blocks(void) { return STATS_MAX_BLOCKS; }
+LOCATE_API int locate_stats_chunk_elems(void) { return MT_CHUNK; }
+LOCATE_API int locate_stats_max_blocks(void) { return mt_grid(0x7fffffff); }
 LOCATE_API size_t locate_stats_workspace_bytes(int n_chunks) { return n_chunks > 0 ? (size_t)n_chunks * sizeof(StatsRecord) : 0; }
 
 // tensors: DEVICE array of n_tensors records {x, n, first_chunk}; chunks: DEVICE array of n_chunks (tensor index, chunk index) int
@@ -187,12 +128,10 @@ LOCATE_API int locate_stats_reduce(const void* tensors, const void* chunks, int 
     LOCATE_REQUIRE(((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(workspace)) & 7) == 0 &&
                        (reinterpret_cast<uintptr_t>(summary) & 3) == 0, "locate_stats_reduce: records and workspace need 8-byte alignment");
     const StatsTensor* T = static_cast<const StatsTensor*>(tensors);
-    int grid = n_chunks < STATS_MAX_BLOCKS ? n_chunks : STATS_MAX_BLOCKS;
-    locate_stats_partial_kernel<<<grid, STATS_THREADS, 0, as_stream(stream)>>>(T, static_cast<const int2*>(chunks), n_tensors, n_chunks,
+    locate_stats_partial_kernel<<<mt_grid(n_chunks), MT_THREADS, 0, as_stream(stream)>>>(T, static_cast<const int2*>(chunks), n_tensors, n_chunks,
                                                                              static_cast<StatsRecord*>(workspace), static_cast<unsigned*>(summary));
     LOCATE_LAUNCH_CHECK("locate_stats_reduce");
-    grid = n_tensors < STATS_MAX_BLOCKS ? n_tensors : STATS_MAX_BLOCKS;
-    locate_stats_combine_kernel<<<grid, STATS_THREADS, 0, as_stream(stream)>>>(T, n_tensors, n_chunks, static_cast<const StatsRecord*>(workspace),
+    locate_stats_combine_kernel<<<mt_grid(n_tensors), MT_THREADS, 0, as_stream(stream)>>>(T, n_tensors, n_chunks, static_cast<const StatsRecord*>(workspace),
                                                                              static_cast<StatsRecord*>(records), static_cast<unsigned*>(summary));
     LOCATE_LAUNCH_CHECK("locate_stats_reduce");
     return LOCATE_OK;

@@ -11,8 +11,9 @@ gradients the step is about to consume (csrc/guard.hip through the C ABI, includ
     at or below `max_norm` gives a scale of exactly 1.
 
 The reference has nothing of the kind.  Like the averaged generator and the run statistics this is opt-in and a separate object
-with kernels of its own: `Nadam` (optim.py, csrc/nadam.hip) is untouched and stays the default.  A guard that has nothing to do
-(finite gradients, no limit or a norm below it) is `Nadam` bit for bit (tests/test_gpu_guard.py).
+with kernels of its own: `Nadam` (optim.py, csrc/nadam.hip) stays the default.  Both steps instantiate one spelled-out update
+(csrc/nadam_step.h), so a guard that has nothing to do (finite gradients, no limit or a norm below it) is `Nadam` bit for bit
+(tests/test_gpu_guard.py).
 
 The verdict needs no host read, so the step can be captured in a hipGraph together with the backward pass (`GraphedTrainStep`);
 the decision is taken anew at every replay.  What the guard did is kept in running counters on the device: `counters()` reads
@@ -27,6 +28,7 @@ import struct
 
 import torch
 
+from ._tables import chunk_pairs, remember, stage
 from .optim import Nadam
 
 COUNTER_KEYS = ("steps", "skipped", "clipped", "consecutive_skips", "last_norm", "last_scale", "last_nonfinite")
@@ -131,24 +133,12 @@ class GuardedNadam(Nadam):
         from ._lib import lib
         L = lib()
         assert L.locate_guard_tensor_record_bytes() == 16
-        chunk = L.locate_guard_chunk_elems()
-        rec, chunks = bytearray(), []
-        for i, p in enumerate(plist):
-            rec += struct.pack("<Qq", p.grad.data_ptr(), p.numel())
-            chunks.extend((i, c) for c in range((p.numel() + chunk - 1) // chunk))
+        rec = b"".join(struct.pack("<Qq", p.grad.data_ptr(), p.numel()) for p in plist)
+        pairs, _ = chunk_pairs([p.numel() for p in plist], L.locate_guard_chunk_elems())
         dev = plist[0].device
-        # pinned staging + async copies, as in Nadam._table: legal inside a hipGraph capture, the host buffers live with the table
-        t_host = torch.frombuffer(rec, dtype=torch.uint8).clone().pin_memory()
-        c_host = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).pin_memory()
-        ws = torch.empty(max(L.locate_guard_workspace_bytes(len(chunks)) // 8, 2), dtype=torch.int64, device=dev)
-        tab = (t_host.to(dev, non_blocking=True), c_host.to(dev, non_blocking=True), len(plist), len(chunks), ws, t_host, c_host)
-        # bounded like Nadam._tables: eagerly every backward may bring new gradient addresses.  Dropping a table frees its device
-        # arrays and the partials workspace, which a graph that captured a step with it still names - as with Nadam's tables, a
-        # captured step's gradients must keep their addresses (GraphedTrainStep's do: one key, never evicted by itself)
-        if len(self._guard_tables) > 8:
-            self._guard_tables.clear()
-        self._guard_tables[key] = tab
-        return tab
+        ws = torch.empty(max(L.locate_guard_workspace_bytes(len(pairs)) // 8, 2), dtype=torch.int64, device=dev)
+        # bounded like Nadam._tables: eagerly every backward may bring new gradient addresses
+        return remember(self._guard_tables, key, stage(rec, pairs, len(plist), dev, scratch=ws), 8)
 
     def _table(self, plist):
         """Nadam's tables for one parameter group - and the guard's, over every gradient the optimizer has now
@@ -163,37 +153,22 @@ class GuardedNadam(Nadam):
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
-        groups = []
-        for group in self.param_groups:
-            plist = []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                    raise TypeError("GuardedNadam: parameters must be contiguous float32 tensors on the MI355X")
-                if not p.grad.is_contiguous():
-                    p.grad = p.grad.contiguous()
-                plist.append(p)
-            if plist:
-                groups.append((group, plist))
+        groups = self._groups_with_gradients()
         if not groups:
             return loss
         from ._lib import check, lib
         ptr = lambda t: ctypes.c_void_p(t.data_ptr())          # noqa: E731
-        g_dev, gc_dev, n_g, n_gc, ws = self._guard_table([p for _, plist in groups for p in plist])[:5]
+        g = self._guard_table([p for _, plist in groups for p in plist])
         verdict = self._record(groups[0][1][0].device)
-        reduce_args = (ptr(g_dev), ptr(gc_dev), n_g, n_gc, ptr(ws))
+        reduce_args = (ptr(g.records), ptr(g.chunks), g.n_tensors, g.n_chunks, ptr(g.scratch))
         for group, plist in groups:
-            t_dev, c_dev, coef, n_t, n_c = Nadam._table(self, plist)[:5]
+            tab = Nadam._table(self, plist)
             b1, b2 = group["betas"]
-            check(lib().locate_guarded_nadam_step(*reduce_args, ptr(verdict), self.max_norm, int(self.skip_nonfinite), ptr(t_dev),
-                                                  ptr(coef), ptr(c_dev), n_t, n_c, float(group["lr"]), float(b1), float(b2),
-                                                  float(group["eps"]), float(group["schedule_decay"]), float(group["weight_decay"]),
-                                                  ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
+            check(lib().locate_guarded_nadam_step(*reduce_args, ptr(verdict), self.max_norm, int(self.skip_nonfinite), ptr(tab.records),
+                                                  ptr(tab.scratch), ptr(tab.chunks), tab.n_tensors, tab.n_chunks, float(group["lr"]),
+                                                  float(b1), float(b2), float(group["eps"]), float(group["schedule_decay"]),
+                                                  float(group["weight_decay"]), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
                   "locate_guarded_nadam_step")
             reduce_args = (None, None, 0, 0, None)          # the later groups of this step apply the same verdict
-            # the kernel writes through raw pointers: tell autograd / the packed-panel cache that the weights changed
-            torch._C._increment_version(plist)
-            for p in plist:
-                p.__dict__["_locate_wmax"][1] = p._version        # the words hold the maximum of THIS version of the weights
+            self._stamp(plist)
         return loss

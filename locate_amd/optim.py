@@ -8,6 +8,7 @@ import struct
 import torch
 
 from ._lib import check, lib
+from ._tables import chunk_pairs, remember, stage
 
 
 class Nadam(torch.optim.Optimizer):
@@ -77,51 +78,49 @@ class Nadam(torch.optim.Optimizer):
             return tab
         L = lib()
         assert L.locate_nadam_tensor_record_bytes() == 56
-        chunk = L.locate_nadam_chunk_elems()
         rec = bytearray()
-        chunks = []
-        for i, p in enumerate(plist):
+        for p in plist:
             st = self._state_for(p)
             rec += struct.pack("<5QqQ", p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                                st["sched"].data_ptr(), p.numel(), self._absmax_words(p).data_ptr())
-            chunks.extend((i, c) for c in range((p.numel() + chunk - 1) // chunk))
+        pairs, _ = chunk_pairs([p.numel() for p in plist], L.locate_nadam_chunk_elems())
         dev = plist[0].device
-        # pinned staging + async copies: legal inside a hipGraph capture (the memcpy nodes re-read these host
-        # buffers on every replay, so they are kept alive with the table)
-        t_host = torch.frombuffer(rec, dtype=torch.uint8).clone().pin_memory()
-        c_host = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).pin_memory()
-        t_dev = t_host.to(dev, non_blocking=True)
-        c_dev = c_host.to(dev, non_blocking=True)
         coef = torch.empty(len(plist) * 4, dtype=torch.float32, device=dev)
-        tab = (t_dev, c_dev, coef, len(plist), len(chunks), t_host, c_host)
-        if len(self._tables) > 8:
-            self._tables.clear()
-        self._tables[key] = tab
-        return tab
+        return remember(self._tables, key, stage(rec, pairs, len(plist), dev, scratch=coef), 8)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = closure() if closure is not None else None
+    def _groups_with_gradients(self):
+        """[(group, its parameters that have a gradient)], the groups without one left out; gradients made contiguous"""
+        groups = []
         for group in self.param_groups:
             plist = []
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                    raise TypeError("Nadam: parameters must be contiguous float32 tensors on the MI355X")
+                    raise TypeError("%s: parameters must be contiguous float32 tensors on the MI355X" % type(self).__name__)
                 if not p.grad.is_contiguous():
                     p.grad = p.grad.contiguous()
                 plist.append(p)
-            if not plist:
-                continue
-            t_dev, c_dev, coef, n_t, n_c = self._table(plist)[:5]
+            if plist:
+                groups.append((group, plist))
+        return groups
+
+    @staticmethod
+    def _stamp(plist):
+        """the kernel wrote through raw pointers: tell autograd / the packed-panel cache that the weights changed"""
+        torch._C._increment_version(plist)
+        for p in plist:
+            p.__dict__["_locate_wmax"][1] = p._version        # the words hold the maximum of THIS version of the weights
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = closure() if closure is not None else None
+        for group, plist in self._groups_with_gradients():
+            tab = self._table(plist)
             b1, b2 = group["betas"]
-            check(lib().locate_nadam_step(t_dev.data_ptr(), coef.data_ptr(), c_dev.data_ptr(), n_t, n_c, float(group["lr"]),
-                                          float(b1), float(b2), float(group["eps"]), float(group["schedule_decay"]),
-                                          float(group["weight_decay"]),
+            check(lib().locate_nadam_step(tab.records.data_ptr(), tab.scratch.data_ptr(), tab.chunks.data_ptr(), tab.n_tensors,
+                                          tab.n_chunks, float(group["lr"]), float(b1), float(b2), float(group["eps"]),
+                                          float(group["schedule_decay"]), float(group["weight_decay"]),
                                           torch.cuda.current_stream().cuda_stream), "locate_nadam_step")
-            # the kernel writes through raw pointers: tell autograd / the packed-panel cache that the weights changed
-            torch._C._increment_version(plist)
-            for p in plist:
-                p.__dict__["_locate_wmax"][1] = p._version        # the words hold the maximum of THIS version of the weights
+            self._stamp(plist)
         return loss

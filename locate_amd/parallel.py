@@ -385,31 +385,26 @@ class GradAllReducer:
         buffers live in the graphs' memory pool)."""
         import struct
         from ._lib import lib
+        from ._tables import chunk_pairs, remember, stage
         key = (b, flat.data_ptr()) + tuple(g.data_ptr() for g in grads)
         tab = self._copy_tables.get(key)
         if tab is None:
             L = lib()
             assert L.locate_multi_copy_record_bytes() == 24
-            chunk = L.locate_multi_copy_chunk_elems()
-            rec, chunks, off = bytearray(), [], 0
-            for i, g in enumerate(grads):
+            rec, off = bytearray(), 0
+            for g in grads:
                 rec += struct.pack("<2Qq", g.data_ptr(), flat.data_ptr() + 4 * off, g.numel())
-                chunks.extend((i, c) for c in range((g.numel() + chunk - 1) // chunk))
                 off += g.numel()
-            t_dev = torch.frombuffer(rec, dtype=torch.uint8).clone().to(flat.device)
-            c_dev = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(flat.device)
-            tab = (t_dev, c_dev, len(chunks))
-            if len(self._copy_tables) > 4 * max(len(self.buckets), 1):
-                self._copy_tables.clear()
-            self._copy_tables[key] = tab
+            pairs, _ = chunk_pairs([g.numel() for g in grads], L.locate_multi_copy_chunk_elems())
+            tab = remember(self._copy_tables, key, stage(rec, pairs, len(grads), flat.device), 4 * max(len(self.buckets), 1))
         return tab
 
     def _pack(self, b, flat, grads):
         # one table-driven launch per bucket (csrc/parallel.hip) instead of one copy per gradient (~140 tensors per network)
         if flat.is_cuda and all(g.is_contiguous() and g.dtype == torch.float32 for g in grads):
             from ._lib import check, lib
-            t_dev, c_dev, n_chunks = self._copy_table(b, flat, grads)
-            check(lib().locate_multi_copy(t_dev.data_ptr(), c_dev.data_ptr(), n_chunks, 0, 1.0,
+            tab = self._copy_table(b, flat, grads)
+            check(lib().locate_multi_copy(tab.records.data_ptr(), tab.chunks.data_ptr(), tab.n_chunks, 0, 1.0,
                                           torch.cuda.current_stream(flat.device).cuda_stream), "locate_multi_copy")
             return
         torch._foreach_copy_(self._views(flat, grads), [g if g.is_contiguous() else g.contiguous() for g in grads])
@@ -530,8 +525,8 @@ class GradAllReducer:
         grads = [self.params[i].grad for i in members]
         if flat.is_cuda and all(g.is_contiguous() and g.dtype == torch.float32 for g in grads):
             from ._lib import check, lib
-            t_dev, c_dev, n_chunks = self._copy_table(b, flat, grads)
-            check(lib().locate_multi_copy(t_dev.data_ptr(), c_dev.data_ptr(), n_chunks, 1, 1.0 if inv is None else float(inv),
+            tab = self._copy_table(b, flat, grads)
+            check(lib().locate_multi_copy(tab.records.data_ptr(), tab.chunks.data_ptr(), tab.n_chunks, 1, 1.0 if inv is None else float(inv),
                                           torch.cuda.current_stream(flat.device).cuda_stream), "locate_multi_copy")
             return
         if inv is not None:

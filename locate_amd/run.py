@@ -77,6 +77,15 @@ def picture_name(sub, i, subepochs, batches):
     return head + ("-END.png" if i is None else "-%0*d.png" % (len(str(batches)), i))
 
 
+def _write_json(path, obj):
+    """to a .tmp, then renamed: a reader never sees half a file"""
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path + ".tmp", "w") as f:
+        json.dump(obj, f)
+    os.replace(path + ".tmp", path)
+    return path
+
+
 class Trainer:
     """step: a `TrainStep`; pipeline: an `InputPipeline`; out: the output folder.
 
@@ -268,23 +277,16 @@ class Trainer:
         seen = {tag: opt.counters() for tag, opt in self._guards()}
         for tag, c in seen.items():
             if c["consecutive_skips"] >= self.max_consecutive_skips:
-                path = os.path.join(self.out, "error", "nonfinite.json")
-                os.makedirs(os.path.dirname(path), exist_ok=True)
-                with open(path + ".tmp", "w") as f:
-                    json.dump({"iteration": self.iterations, "epoch": self.epoch + 1, "tensors": [],
-                               "guard": {"network": tag, "counters": c}}, f)
-                os.replace(path + ".tmp", path)
-                self.written.append(path)
+                self._write_nonfinite({"iteration": self.iterations, "epoch": self.epoch + 1, "tensors": [],
+                                       "guard": {"network": tag, "counters": c}})
                 raise GuardExhausted(self.iterations, tag, c["consecutive_skips"])
         return seen
 
     def _save_guards(self, epoch):
-        path = os.path.join(self.out, "error", "%d-guard.json" % epoch)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        with open(path + ".tmp", "w") as f:
-            json.dump(self._check_guards(), f)
-        os.replace(path + ".tmp", path)
-        return path
+        return _write_json(os.path.join(self.out, "error", "%d-guard.json" % epoch), self._check_guards())
+
+    def _write_nonfinite(self, record):
+        self.written.append(_write_json(os.path.join(self.out, "error", "nonfinite.json"), record))
 
     def _check_stats(self, before_save=False):
         """stats.check(); before a save, preceded by a record of the state that is about to be saved if it has none.  A run that
@@ -295,12 +297,7 @@ class Trainer:
         try:
             self.stats.check()
         except NonFiniteError as err:
-            path = os.path.join(self.out, "error", "nonfinite.json")
-            os.makedirs(os.path.dirname(path), exist_ok=True)
-            with open(path + ".tmp", "w") as f:
-                json.dump({"iteration": err.iteration, "epoch": self.epoch + 1, "tensors": [list(t) for t in err.tensors]}, f)
-            os.replace(path + ".tmp", path)
-            self.written.append(path)
+            self._write_nonfinite({"iteration": err.iteration, "epoch": self.epoch + 1, "tensors": [list(t) for t in err.tensors]})
             raise
 
     # ---- the loop -------------------------------------------------------------------------------------------
@@ -347,7 +344,6 @@ class Trainer:
         """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
         value = self.swd.evaluate(self.gen)
         path = os.path.join(self.out, "error", "swd.json")
-        os.makedirs(os.path.dirname(path), exist_ok=True)
         records = []
         if os.path.exists(path):
             with open(path) as f:
@@ -356,10 +352,7 @@ class Trainer:
         if self.average is not None:
             value = self.swd.evaluate(self.average.generator)
             records[-1]["average"] = {"levels": value["levels"], "mean": value["mean"]}
-        with open(path + ".tmp", "w") as f:
-            json.dump(records, f)
-        os.replace(path + ".tmp", path)
-        return path
+        return _write_json(path, records)
 
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);

@@ -26,6 +26,8 @@ import struct
 import numpy as np
 import torch
 
+from ._tables import chunk_pairs, stage
+
 
 class NonFiniteError(RuntimeError):
     """A record holds NaN or Inf.  `iteration`: that of the first such record; `tensors`: [(name, count), ...] of that record,
@@ -50,21 +52,15 @@ def _require_device_tensors(tensors, what):
 
 
 def _device_table(tensors):
-    """(records, chunks, n_tensors, n_chunks, workspace, host buffers...) of locate_stats_reduce for non-empty device tensors.
-    Staged from pinned memory with async copies, as in Nadam._table; the host buffers are kept alive with the table."""
+    """The table (_tables.Table, the workspace as its `scratch`) of locate_stats_reduce for non-empty device tensors."""
     from ._lib import lib
     L = lib()
     assert L.locate_stats_tensor_record_bytes() == 24 and L.locate_stats_record_bytes() == 16
-    chunk = L.locate_stats_chunk_elems()
-    rec, chunks = bytearray(), []
-    for i, t in enumerate(tensors):
-        rec += struct.pack("<Qqi4x", t.data_ptr(), t.numel(), len(chunks))
-        chunks.extend((i, c) for c in range((t.numel() + chunk - 1) // chunk))
+    pairs, first = chunk_pairs([t.numel() for t in tensors], L.locate_stats_chunk_elems())
+    rec = b"".join(struct.pack("<Qqi4x", t.data_ptr(), t.numel(), at) for t, at in zip(tensors, first))
     dev = tensors[0].device
-    t_host = torch.frombuffer(rec, dtype=torch.uint8).clone().pin_memory()
-    c_host = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).pin_memory()
-    ws = torch.empty(max(L.locate_stats_workspace_bytes(len(chunks)) // 8, 2), dtype=torch.int64, device=dev)
-    return (t_host.to(dev, non_blocking=True), c_host.to(dev, non_blocking=True), len(tensors), len(chunks), ws, t_host, c_host)
+    ws = torch.empty(max(L.locate_stats_workspace_bytes(len(pairs)) // 8, 2), dtype=torch.int64, device=dev)
+    return stage(rec, pairs, len(tensors), dev, scratch=ws)
 
 
 def _launch(table, row):

@@ -922,6 +922,95 @@ def test_nadam_golden():
             assert_close(p.detach().cpu(), z["p%d_%d" % (i, step)], 2e-6, "p%d step %d" % (i, step))
 
 
+def test_nadam_step_keeps_its_recorded_bits():
+    """Three `Nadam` steps at weight decay 0 and 0.01 on the case of tests/helpers/nadam_bits.py (1, 3, 4095, 4097 elements, a
+    4100-element parameter that is only 4-byte aligned, a parameter without a gradient; a zero and a denormal among the gradients)
+    against tests/golden/p01_nadam_bits.npz - this project's own output, recorded by tools/record_nadam_bits.py before the update
+    moved into csrc/nadam_step.h: p, exp_avg, exp_avg_sq and sched after the last step in full, a SHA-256 per tensor of the steps
+    before it.  Equality of bits."""
+    import os
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
+    import nadam_bits as NB
+    z = load_golden("p01_nadam_bits")
+    seen = set()
+    for k, wd in enumerate(NB.WEIGHT_DECAYS):
+        got = NB.run(wd, dev())
+        assert got["frame"].tolist() == [7.0] * 8 + [0.0, 1.0, 2.0, 3.0, 4.0], "a word outside the stepped tensors was written"
+        for key, a in got.items():
+            name = "wd%d/%s" % (k, key)
+            if name in z.files:
+                want = z[name]
+                assert a.dtype == want.dtype and a.shape == want.shape, name
+                word = np.uint32 if a.dtype == np.float32 else np.uint64
+                differ = int((a.view(word) != want.view(word)).sum())
+                print("%s: %d of %d elements differ" % (name, differ, a.size))
+                assert differ == 0, "%s: %d of %d elements differ in their bits" % (name, differ, a.size)
+            else:
+                name += "/sha256"
+                assert NB.sha(a) == str(z[name]), name
+            seen.add(name)
+    assert seen == set(z.files) and len(seen) == 2 * (NB.STEPS * len(NB.KINDS) * len(NB.SIZES) + 1)
+
+
+@pytest.mark.parametrize("lead", [0, 1])
+def test_multi_copy_packs_and_unpacks_bit_for_bit(lead):
+    """locate_multi_copy through the raw C ABI: gradients of 1, 4095 and 4097 elements packed into a flat buffer - the second lands
+    4 bytes behind the buffer's start, the third's last chunk holds one element; with lead = 1 the buffer itself starts one element
+    into its allocation, so that every place is only 4-byte aligned.  Pack equals torch's copies, unpack equals ONE fp32
+    multiplication per element (scales 0.5 and 1/3), both bit for bit; the words around every written range keep their sentinel."""
+    import struct
+    from locate_amd._lib import check, lib
+    from locate_amd._tables import chunk_pairs
+    L = lib()
+    assert L.locate_multi_copy_record_bytes() == 24
+    sizes, sentinel, guard = (1, 4095, 4097), 0x7FC0DEAD, 64
+    total = sum(sizes)
+    rng = np.random.default_rng(11)
+    host = [rng.standard_normal(n).astype(np.float32) for n in sizes]
+    host[1][5], host[2][4096] = np.float32(-0.0), np.float32(3e38)
+    grads = [G_(a) for a in host]
+    pairs, _ = chunk_pairs(sizes, L.locate_multi_copy_chunk_elems())
+    c_dev = torch.tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev())
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def table(tensors, flat):
+        rec, off = bytearray(), 0
+        for t in tensors:
+            rec += struct.pack("<2Qq", t.data_ptr(), flat.data_ptr() + 4 * off, t.numel())
+            off += t.numel()
+        return torch.frombuffer(rec, dtype=torch.uint8).clone().to(dev())
+
+    arena = torch.full((lead + total + guard,), sentinel, dtype=torch.int32, device=dev())
+    flat = arena[lead:lead + total].view(torch.float32)
+    t_dev = table(grads, flat)
+    check(L.locate_multi_copy(t_dev.data_ptr(), c_dev.data_ptr(), len(pairs), 0, 1.0, stream), "locate_multi_copy")
+    want = torch.cat(grads)
+    assert torch.equal(flat.view(torch.int32), want.view(torch.int32))
+    assert (arena[:lead] == sentinel).all() and (arena[lead + total:] == sentinel).all(), "a word outside the flat buffer was written"
+    assert all(torch.equal(g.cpu(), T(a)) for g, a in zip(grads, host))          # packing only reads the gradients
+
+    for scale in (0.5, 1.0 / 3.0):
+        room = torch.full((total + guard * (len(sizes) + 1),), sentinel, dtype=torch.int32, device=dev())
+        outs, at = [], guard
+        for n in sizes:
+            outs.append(room[at:at + n].view(torch.float32))
+            at += n + guard
+        t_dev = table(outs, flat)
+        check(L.locate_multi_copy(t_dev.data_ptr(), c_dev.data_ptr(), len(pairs), 1, scale, stream), "locate_multi_copy")
+        for out, a in zip(outs, host):
+            expect = a * np.float32(scale)          # numpy float32: one correctly rounded multiplication
+            assert np.array_equal(out.cpu().numpy().view(np.uint32), expect.view(np.uint32))
+        written = torch.zeros(room.numel(), dtype=torch.bool, device=dev())
+        at = guard
+        for n in sizes:
+            written[at:at + n] = True
+            at += n + guard
+        assert (room[~written] == sentinel).all(), "a word outside the gradients was written"
+        assert torch.equal(flat.view(torch.int32), want.view(torch.int32)) and (arena[lead + total:] == sentinel).all()
+
+
 def test_loss_kernels():
     from locate_amd.train import d_loss, g_loss
     from oracle import locate_oracle as O
