@@ -401,6 +401,37 @@ int locate_guarded_nadam_step(const void* grads, const void* grad_chunks, int n_
                               int n_chunks, double lr, double beta1, double beta2, double eps, double schedule_decay, double weight_decay,
                               void* stream);
 
+/* ---- last-good copy of a training state in device memory (no reference counterpart): every tensor of a table into one of two
+ *      slots in one pass that also classifies every 4-byte word it copies, and a one-block commit behind it.
+ *      records: DEVICE array of {uint32* live; int64 offset; int64 n; int32 kind; uint32 fill[4]; int32 pad} records
+ *      (locate_snapshot_record_bytes() = 48): live may be NULL (the tensor does not exist yet) and needs 4-byte alignment only;
+ *      offset: BYTES into a slot, a multiple of 16; n: 4-byte words; kind: how a word is judged - 0 never, 1 fp32 (exponent field
+ *      all ones), 2 fp64 (n even: the exponent field of the HIGH word of each pair all ones, the low word is not looked at).
+ *      chunks: DEVICE (tensor index, chunk index) int pairs in pieces of locate_snapshot_chunk_elems() words.
+ *      slot0, slot1: 16-byte aligned, distinct, each at least max(offset + 4 n) bytes.
+ *      commit: locate_snapshot_commit_bytes() = 64 bytes, 8-byte aligned, read and written:
+ *        {int32 good; int32 bad_tensor; uint64 bad_words; int64 iteration, taken, rejected, last_rejected_iteration,
+ *         last_rejected_count; int32 last_rejected_tensor; int32 pad}
+ *        set ONCE by the caller to good = -1, bad_tensor = INT32_MAX, last_rejected_tensor = -1, everything else 0.
+ *      locate_snapshot_take, two launches: (1) copies every tensor bit for bit (NaN payloads, denormals, -0.0) to its offset in
+ *      the slot that is not `good` (slot0 when good == -1) - for a NULL live pointer the four fill words, repeating - and counts
+ *      the words that are non-finite for their kind: blocks that found one add their count to bad_words and fold the lowest such
+ *      tensor index into bad_tensor (one integer atomic each per block; no floating-point atomics; a clean take issues none);
+ *      (2) one block: bad_words == 0: good = the slot just written, iteration = `iteration`, taken += 1; otherwise good and
+ *      iteration stay, rejected += 1, last_rejected_{iteration, count, tensor} are stored.  bad_words and bad_tensor are reset:
+ *      the record is ready for the next take.  16-byte accesses where live is 16-byte aligned; every load of a chunk is issued
+ *      before its first store.  Writes the destination slot and the commit record and nothing else; the live tensors and the
+ *      good slot are only read.  No allocation, host read or synchronisation: legal under stream capture, where the decision
+ *      is taken at every replay.
+ *      locate_snapshot_restore: `slot` (the caller chooses: slot `good`) back into the live tensors; writes exactly
+ *      [live, live + n) of every record whose live pointer is not NULL. ---- */
+size_t locate_snapshot_record_bytes(void);
+size_t locate_snapshot_commit_bytes(void);
+int locate_snapshot_chunk_elems(void);
+int locate_snapshot_take(const void* records, const void* chunks, int n_tensors, int n_chunks, void* slot0, void* slot1, void* commit,
+                         long long iteration, void* stream);
+int locate_snapshot_restore(const void* records, const void* chunks, int n_tensors, int n_chunks, const void* slot, void* stream);
+
 /* ---- loss glue (main.py:149-156,164-169, libs/utils.py:133-134, libs/grad_penalty.py:1-2): values and the
  *      gradients w.r.t. the discriminator outputs ---- */
 int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, float* losses,

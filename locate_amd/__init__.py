@@ -17,6 +17,7 @@ from .metric import (SlicedWasserstein, descriptor_stats, laplacian_pyramid, pro
 from .average import AveragedGenerator, average_weight  # noqa: F401
 from .stats import NonFiniteError, RunStatistics, tensor_statistics  # noqa: F401
 from .guard import GuardedNadam, GuardExhausted  # noqa: F401
+from .snapshot import NoSnapshot, StateSnapshot, TrainingSnapshot, arena_layout  # noqa: F401
 
 
 def __getattr__(name):

@@ -136,6 +136,11 @@ PROTOTYPES = {
     "locate_guard_max_blocks": (c_i, []),
     "locate_guard_workspace_bytes": (c_sz, [c_i]),
     "locate_guarded_nadam_step": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_d, c_i, c_p, c_p, c_p, c_i, c_i, c_d, c_d, c_d, c_d, c_d, c_d, c_p]),
+    "locate_snapshot_record_bytes": (c_sz, []),
+    "locate_snapshot_commit_bytes": (c_sz, []),
+    "locate_snapshot_chunk_elems": (c_i, []),
+    "locate_snapshot_take": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i64, c_p]),
+    "locate_snapshot_restore": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
     "locate_d_loss": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "locate_g_loss": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "locate_input_param_record_bytes": (c_sz, []),

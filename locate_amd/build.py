@@ -15,9 +15,9 @@ LIB = os.path.join(CSRC, "liblocate_hip.so")
 # tests/test_gpu_ops.py::test_bf16x6_kernels_match_fp32_mfma_kernels and the A/B tools).  Loaded only when
 # LOCATE_HIP_DEBUG_LIBRARY=1 is set before `import locate_amd`; the product library has no such switch compiled in.
 LIB_DBG = os.path.join(CSRC, "liblocate_hip_dbg.so")
-DBG_SOURCES = ["conv.hip", "convwgrad.hip", "convwin.hip"]
+DBG_SOURCES = ["conv.hip", "convwgrad.hip", "convwin.hip", "snapshot.hip"]
 SOURCES = ["runtime.hip", "elementwise.hip", "norm.hip", "softmax.hip", "resample.hip", "spectral.hip", "conv.hip", "convpack.hip", "convwgrad.hip", "convwin.hip", "convfp8.hip",
-           "grouped.hip", "nadam.hip", "loss.hip", "finalise.hip", "parallel.hip", "input.hip", "grid.hip", "swd.hip", "average.hip", "stats.hip", "guard.hip"]
+           "grouped.hip", "nadam.hip", "loss.hip", "finalise.hip", "parallel.hip", "input.hip", "grid.hip", "swd.hip", "average.hip", "stats.hip", "guard.hip", "snapshot.hip"]
 ARCH = "gfx950"
 
 

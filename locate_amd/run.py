@@ -6,6 +6,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
                              [--swd-images 0] [--ema-half-life 0] [--stats-every 0]
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
+                             [--rollback-every 0] [--max-rollbacks 3]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -35,7 +36,12 @@ Differences from the reference, all additions:
     `GuardedNadam` (`locate_amd.guard`) instead of `Nadam`: a step whose gradients hold a NaN or an Inf is skipped on the device
     (unless `--no-skip-nonfinite`), and with X > 0 the gradients are scaled down to the global norm X.  `OUT/error/{epoch}-guard.json`
     holds both optimizers' counters, `OUT/trainer.torch` carries them through `--resume`, and a run whose optimizer has skipped
-    `--max-consecutive-skips` steps in a row stops with `GuardExhausted` like a run that holds a NaN does."""
+    `--max-consecutive-skips` steps in a row stops with `GuardExhausted` like a run that holds a NaN does;
+  * `snapshot=` / `--rollback-every N` (off by default; needs `--stats-every` or a guarded optimizer, or nothing would ever notice a
+    failure): a last-good copy of the whole training state is kept in device memory (`locate_amd.snapshot`), renewed at the
+    progress line once N iterations lie behind the last one.  Where the run would stop with `NonFiniteError` or `GuardExhausted`
+    it returns to that copy instead and goes on with the next batches - at most `--max-rollbacks` times, recorded in
+    `OUT/error/rollbacks.json`; after that it stops as before.  Two more copies of weights and moments in device memory."""
 import argparse
 import json
 import os
@@ -144,12 +150,27 @@ class Trainer:
     {"iteration", "epoch", "tensors": [], "guard": {"network", "counters"}} - does NOT save the state and raises
     `GuardExhausted(.iteration, .network)`.  Once per epoch `out/error/{e+1}-guard.json` - {"G": counters, "D": counters}, the
     guarded ones only - is written beside the loss curves; save_state() puts the counters under "guard" in trainer.torch and
-    resume() restores them."""
+    resume() restores them.
+
+    snapshot: a `TrainingSnapshot` over `step` (and `average`), or None (the default: nothing below happens, and every file, record
+    and key is what it is without this argument).  It needs `stats` or a guarded optimizer - nothing else ever notices a failure -
+    and raises ValueError without.  `snapshot.take(iterations)` follows the checks of a progress line once they have passed and at
+    least `rollback_every` iterations lie behind the last take (or the start of the run): two launches on the same stream, no host
+    read; the take commits itself on the device only if every word it copied is finite.  Where the checks above would stop the run
+    - at the progress line and before each save - the trainer instead calls `snapshot.restore()`, while the rollbacks so far
+    (counted across resumes) are fewer than `max_rollbacks` and a committed snapshot exists, appends {"iteration", "to_iteration",
+    "epoch", "cause": "nonfinite" | "guard", "tensors" or "guard"} to the list in `out/error/rollbacks.json` and goes on with the
+    NEXT batches: the pipeline, the latent stream, i, `iterations`, the loss history and the statistics records are not rewound,
+    and the bad record stays in `{e+1}-stats.npz` as evidence.  Before a save the restored state is recorded and checked like any
+    other, then saved.  `nonfinite.json` is written only when the run does stop.  trainer.torch gains "rollbacks"; a resumed run
+    starts with no committed slot.  Limits: a state that is finite but already diverging can be committed - the run then fails
+    again after the rollback and stops once `max_rollbacks` is used up; data parallelism is out of scope (`TrainingSnapshot`)."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
-                 average=None, stats=None, stats_every=16, max_consecutive_skips=16):
+                 average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
+                 max_rollbacks=3):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -189,6 +210,14 @@ class Trainer:
         if int(max_consecutive_skips) < 1:
             raise ValueError("max_consecutive_skips must be >= 1, got %r" % (max_consecutive_skips,))
         self.max_consecutive_skips = int(max_consecutive_skips)
+        if int(rollback_every) < 1 or int(max_rollbacks) < 0:
+            raise ValueError("rollback_every must be >= 1 and max_rollbacks >= 0, got %r and %r" % (rollback_every, max_rollbacks))
+        self.snapshot, self.rollback_every, self.max_rollbacks = snapshot, int(rollback_every), int(max_rollbacks)
+        if snapshot is not None and stats is None and not self._guards():
+            raise ValueError("a snapshot needs `stats` or a guarded optimizer: nothing else would ever trigger a rollback")
+        self.rollbacks = 0          # counted across resumes
+        self._last_take = 0          # `iterations` at the last take (at the start of the run, before the first)
+        self._unrecorded = False          # a restored state that the statistics have not seen yet
         self.epoch, self.sub, self.i, self.iterations = 0, 0, 0, 0
         self._runner = None
         self.written = []
@@ -239,6 +268,8 @@ class Trainer:
             state["average"] = self.average.state_dict()
         if self._guards():
             state["guard"] = {tag: opt.counters_state() for tag, opt in self._guards()}
+        if self.snapshot is not None:
+            state["rollbacks"] = int(self.rollbacks)
         path = os.path.join(self.out, STATE_FILE)
         torch.save(state, path + ".tmp")
         os.replace(path + ".tmp", path)
@@ -264,6 +295,9 @@ class Trainer:
         for tag, opt in self._guards():
             if tag in state.get("guard", {}):
                 opt.load_counters_state(state["guard"][tag])
+        if self.snapshot is not None:
+            self.rollbacks = int(state.get("rollbacks", 0))
+        self._last_take = self.iterations          # no committed slot yet: the first take is rollback_every iterations away
         return self
 
     def _guards(self):
@@ -277,8 +311,10 @@ class Trainer:
         seen = {tag: opt.counters() for tag, opt in self._guards()}
         for tag, c in seen.items():
             if c["consecutive_skips"] >= self.max_consecutive_skips:
-                self._write_nonfinite({"iteration": self.iterations, "epoch": self.epoch + 1, "tensors": [],
-                                       "guard": {"network": tag, "counters": c}})
+                guard = {"network": tag, "counters": c}
+                if self._rollback({"iteration": self.iterations, "cause": "guard", "guard": guard}):
+                    return {tag: opt.counters() for tag, opt in self._guards()}          # consecutive_skips restarted at 0
+                self._write_nonfinite({"iteration": self.iterations, "epoch": self.epoch + 1, "tensors": [], "guard": guard})
                 raise GuardExhausted(self.iterations, tag, c["consecutive_skips"])
         return seen
 
@@ -292,13 +328,56 @@ class Trainer:
         """stats.check(); before a save, preceded by a record of the state that is about to be saved if it has none.  A run that
         holds a non-finite value leaves out/error/nonfinite.json and raises."""
         from .stats import NonFiniteError
-        if before_save and self.iterations > 0 and self.stats.last_iteration != self.iterations:
-            self.stats.record(self.iterations)
+        while True:
+            if before_save and self.iterations > 0 and (self.stats.last_iteration != self.iterations or self._unrecorded):
+                self._record_stats()
+            try:
+                self.stats.check()
+                return
+            except NonFiniteError as err:
+                tensors = [list(t) for t in err.tensors]
+                if not self._rollback({"iteration": err.iteration, "cause": "nonfinite", "tensors": tensors}):
+                    self._write_nonfinite({"iteration": err.iteration, "epoch": self.epoch + 1, "tensors": tensors})
+                    raise
+            if not before_save:
+                return          # rolled back: the run goes on; before a save the restored state is recorded and checked too
+
+    def _record_stats(self):
+        self.stats.record(self.iterations)          # two launches on this stream, no host read
+        self._unrecorded = False
+
+    def _checks(self, before_save=False):
+        """The statistics' and the guards' checks, where the loop reads from the device anyway and before every save."""
+        if self.stats is not None:
+            self._check_stats(before_save)
+        if self._guards():
+            self._check_guards()
+            if before_save and self.stats is not None and self._unrecorded:          # the guard rolled the run back just now
+                self._check_stats(before_save)
+
+    def _rollback(self, record):
+        """Back to the last good snapshot instead of stopping: True when the run now holds that state (one more record in
+        out/error/rollbacks.json), False when it has to stop as it would without a snapshot."""
+        if self.snapshot is None or self.rollbacks >= self.max_rollbacks:
+            return False
+        from .snapshot import NoSnapshot
         try:
-            self.stats.check()
-        except NonFiniteError as err:
-            self._write_nonfinite({"iteration": err.iteration, "epoch": self.epoch + 1, "tensors": [list(t) for t in err.tensors]})
-            raise
+            to_iteration = self.snapshot.restore()
+        except NoSnapshot:
+            return False
+        self.rollbacks += 1
+        self._unrecorded = True
+        path = os.path.join(self.out, "error", "rollbacks.json")
+        records = []
+        if os.path.exists(path):
+            with open(path) as f:
+                records = json.load(f)
+        head = {"iteration": record.pop("iteration"), "to_iteration": int(to_iteration), "epoch": self.epoch + 1}
+        records.append(dict(head, **record))
+        path = _write_json(path, records)
+        if path not in self.written:
+            self.written.append(path)
+        return True
 
     # ---- the loop -------------------------------------------------------------------------------------------
     def _iteration(self):
@@ -321,10 +400,11 @@ class Trainer:
     def _progress(self, e, sub, i, first, subepochs, batches, started):
         """first: the position this call of run() entered the sub-pass at (not 0 after a resume): the rate counts from there"""
         pairs = self.history.flush()          # the one host read of the losses
-        if self.stats is not None:
-            self._check_stats()
-        if self._guards():
-            self._check_guards()
+        before = self.rollbacks
+        self._checks()
+        if self.snapshot is not None and self.rollbacks == before and self.iterations - self._last_take >= self.rollback_every:
+            self.snapshot.take(self.iterations)          # two launches on this stream, no host read; commits itself if finite
+            self._last_take = self.iterations
         if self.log is None or not (self.history.d and self.history.g):
             return
         rate = (i - first) / max(time.time() - started, 1e-9)
@@ -368,10 +448,7 @@ class Trainer:
                 self.loop.i = self.i          # i restarts at 1 in every sub-pass (main.py:140)
                 while self.i < batches:
                     if self.max_iterations is not None and self.iterations >= self.max_iterations:
-                        if self.stats is not None:
-                            self._check_stats(before_save=True)
-                        if self._guards():
-                            self._check_guards()
+                        self._checks(before_save=True)
                         self.written += self.save_state()
                         return self.iterations
                     out = self._iteration()
@@ -380,7 +457,7 @@ class Trainer:
                     self.i += 1
                     self.iterations += 1
                     if self.stats is not None and self.stats_every and self.iterations % self.stats_every == 0:
-                        self.stats.record(self.iterations)          # two launches on this stream, no host read
+                        self._record_stats()
                     i = self.i
                     if i % miniter == 0:          # main.py:158
                         self.history.record(out)
@@ -440,6 +517,11 @@ def main(argv=None):
                     help="step both networks with GuardedNadam but take a step whose gradients hold a NaN or an Inf (it is counted)")
     ap.add_argument("--max-consecutive-skips", type=int, default=16, metavar="N",
                     help="stop with an error, before anything is saved, once a guarded optimizer has skipped N steps in a row")
+    ap.add_argument("--rollback-every", type=int, default=0, metavar="N",
+                    help="keep a last-good copy of the training state in device memory, renewed once N iterations lie behind the last "
+                         "one, and return to it instead of stopping on a NaN or an exhausted guard (OUT/error/rollbacks.json); needs "
+                         "--stats-every or a guarded optimizer; 0: off")
+    ap.add_argument("--max-rollbacks", type=int, default=3, metavar="N", help="stop as without --rollback-every after N rollbacks")
     args = ap.parse_args(argv)
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
@@ -447,6 +529,12 @@ def main(argv=None):
         ap.error("--clip-grad-norm must be finite and >= 0")
     if args.max_consecutive_skips < 1:
         ap.error("--max-consecutive-skips must be >= 1")
+    if args.rollback_every < 0 or args.max_rollbacks < 0:
+        ap.error("--rollback-every and --max-rollbacks must be >= 0")
+    guarded_step = args.clip_grad_norm is not None or args.no_skip_nonfinite
+    if args.rollback_every > 0 and not (args.stats_every > 0 or guarded_step):
+        ap.error("--rollback-every needs --stats-every or a guarded optimizer (--clip-grad-norm / --no-skip-nonfinite): "
+                 "nothing else would ever trigger a rollback")
 
     from . import DeviceImageStore, Discriminator, Generator, InputPipeline, NetConfig, TrainStep, get_model
     from ._lib import require_gpu
@@ -456,7 +544,7 @@ def main(argv=None):
     torch.manual_seed(cfg.seed)
     gen, gen_opt = get_model(Generator(cfg), cfg.glr, dev, cfg)
     dis, dis_opt = get_model(Discriminator(cfg), cfg.dlr, dev, cfg)
-    if args.clip_grad_norm is not None or args.no_skip_nonfinite:
+    if guarded_step:
         from .guard import GuardedNadam
         guarded = dict(max_norm=args.clip_grad_norm or 0.0, skip_nonfinite=not args.no_skip_nonfinite)
         # over get_model's own parameter groups: whatever it sets for Nadam (lr, betas, ...) holds for the guarded step too
@@ -485,9 +573,14 @@ def main(argv=None):
     if args.stats_every > 0:
         from .stats import RunStatistics
         stats = RunStatistics(gen, dis)
+    snapshot = None
+    if args.rollback_every > 0:
+        from .snapshot import TrainingSnapshot
+        snapshot = TrainingSnapshot(step, average=average)
     trainer = Trainer(step, pipeline, args.out, epochs=args.epochs, max_iterations=args.max_iterations, images=args.images,
                       seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average, stats=stats,
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
+                      snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
