@@ -432,6 +432,21 @@ int locate_snapshot_take(const void* records, const void* chunks, int n_tensors,
                          long long iteration, void* stream);
 int locate_snapshot_restore(const void* records, const void* chunks, int n_tensors, int n_chunks, const void* slot, void* stream);
 
+/* ---- 128-bit digests of every tensor of a device table, over 4-byte words, modulo 2^64 (no reference counterpart; what the
+ *      snapshot's spill to disk checks a copy against, locate_amd/spill.py):  A = sum_i w_i,  B = sum_i ((i + 1) mod 2^32) * w_i.
+ *      records: DEVICE array of {const uint32* p; int64 n} records (locate_digest_record_bytes() = 16); p needs 4-byte alignment
+ *      only; n may be 0.  chunks: DEVICE (tensor index, chunk index) int pairs in pieces of locate_digest_chunk_elems() words, a
+ *      tensor's pairs consecutive and in order.  first: DEVICE int32[n_tensors + 1], the position of each tensor's first pair,
+ *      n_chunks at the end.  partials: n_chunks x 16 bytes, out: n_tensors x {uint64 A, uint64 B}, both 8-byte aligned.
+ *      Two launches: one {A, B} partial per pair (a damaged pair writes zeros), then each tensor's partials over
+ *      [first[t], first[t + 1]) added into out[t].  Integer sums only, no atomics, nothing to clear between calls: the result
+ *      depends on nothing but the words and their order.  No allocation, host read or synchronisation: legal under stream
+ *      capture.  Only partials and out are written. ---- */
+size_t locate_digest_record_bytes(void);
+int locate_digest_chunk_elems(void);
+int locate_digest(const void* records, const void* chunks, const void* first, int n_tensors, int n_chunks, void* partials, void* out,
+                  void* stream);
+
 /* ---- loss glue (main.py:149-156,164-169, libs/utils.py:133-134, libs/grad_penalty.py:1-2): values and the
  *      gradients w.r.t. the discriminator outputs ---- */
 int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, float* losses,

@@ -141,6 +141,9 @@ PROTOTYPES = {
     "locate_snapshot_chunk_elems": (c_i, []),
     "locate_snapshot_take": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i64, c_p]),
     "locate_snapshot_restore": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p]),
+    "locate_digest_record_bytes": (c_sz, []),
+    "locate_digest_chunk_elems": (c_i, []),
+    "locate_digest": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
     "locate_d_loss": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "locate_g_loss": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "locate_input_param_record_bytes": (c_sz, []),
@@ -166,7 +169,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 12
+EXPECTED_ABI = 13
 
 
 _lib = None

@@ -6,7 +6,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
                              [--swd-images 0] [--ema-half-life 0] [--stats-every 0]
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
-                             [--rollback-every 0] [--max-rollbacks 3]
+                             [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -41,7 +41,11 @@ Differences from the reference, all additions:
     failure): a last-good copy of the whole training state is kept in device memory (`locate_amd.snapshot`), renewed at the
     progress line once N iterations lie behind the last one.  Where the run would stop with `NonFiniteError` or `GuardExhausted`
     it returns to that copy instead and goes on with the next batches - at most `--max-rollbacks` times, recorded in
-    `OUT/error/rollbacks.json`; after that it stops as before.  Two more copies of weights and moments in device memory."""
+    `OUT/error/rollbacks.json`; after that it stops as before.  Two more copies of weights and moments in device memory;
+  * `spill_every=` / `--spill-every N` (off by default; needs `--rollback-every`): once N iterations lie behind the last one, the
+    committed snapshot goes to `OUT/spill/spill-K.bin` in the background (`locate_amd.spill`) - the training stream does not wait -
+    and `--resume` continues from that file, bit for bit, when it is newer than the last `trainer.torch`: a killed job loses
+    minutes, not the epoch.  One pinned host buffer of a snapshot slot's size."""
 import argparse
 import json
 import os
@@ -164,13 +168,27 @@ class Trainer:
     and the bad record stays in `{e+1}-stats.npz` as evidence.  Before a save the restored state is recorded and checked like any
     other, then saved.  `nonfinite.json` is written only when the run does stop.  trainer.torch gains "rollbacks"; a resumed run
     starts with no committed slot.  Limits: a state that is finite but already diverging can be committed - the run then fails
-    again after the rollback and stops once `max_rollbacks` is used up; data parallelism is out of scope (`TrainingSnapshot`)."""
+    again after the rollback and stops once `max_rollbacks` is used up; data parallelism is out of scope (`TrainingSnapshot`).
+
+    spill_every: 0 (the default: nothing below happens, and every file, record and key is what it is without this argument) or N > 0,
+    which needs `snapshot` and raises ValueError without.  The trainer makes a `SnapshotSpill(snapshot, out/spill)`.  At a progress
+    line, after the checks have passed and BEFORE the take that follows them, `spill.begin()` runs once at least N iterations lie
+    behind the last spill begun: what goes to disk is the slot committed at an EARLIER progress line - finite at its take, and the
+    run has passed its checks again since.  The take itself goes through `spill.take`, whose host state is what save_state() puts
+    into trainer.torch and netG.extra.torch, as of that take: epoch, sub, i, iterations, the pipeline's, the latent generator's
+    and the loss history's state, the fixed latents, the average's `updates` and `one_minus_beta`, the guards' counters,
+    `rollbacks`, `gen.noise` (constant: copied to the host once, at construction) and the `dis_uv_trainable` flag.  resume() compares
+    `SnapshotSpill.latest(out/spill)` with trainer.torch - which may then be missing - and continues from the one with more
+    `iterations`: from a spill through `restore_training_state`, with the host state restored exactly as trainer.torch's is; the
+    choice goes into `out/error/resumes.json` as {"from": "spill" | "save", "iterations"}.  run() calls `spill.wait()` before it
+    returns or re-raises, so a run that ends normally leaves no half-started writer.  Out of scope: data parallelism, compression,
+    an asynchronous save_state(), bit-exact graphed resumes (two warm-up iterations per resume, as today)."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
-                 max_rollbacks=3):
+                 max_rollbacks=3, spill_every=0):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -215,6 +233,18 @@ class Trainer:
         self.snapshot, self.rollback_every, self.max_rollbacks = snapshot, int(rollback_every), int(max_rollbacks)
         if snapshot is not None and stats is None and not self._guards():
             raise ValueError("a snapshot needs `stats` or a guarded optimizer: nothing else would ever trigger a rollback")
+        if int(spill_every) < 0:
+            raise ValueError("spill_every must be >= 0, got %r" % (spill_every,))
+        self.spill_every = int(spill_every)
+        if self.spill_every and snapshot is None:
+            raise ValueError("spill_every needs a snapshot: what goes to disk is its committed slot")
+        self.spill = None
+        if self.spill_every:
+            from .spill import SnapshotSpill
+            self.spill = SnapshotSpill(snapshot, os.path.join(self.out, "spill"))
+            self._noise_host = self.gen.noise.detach().to("cpu").clone()          # constant during training
+            self._fixed_noise_host = None
+        self._last_spill = 0          # `iterations` at the last spill begun
         self.rollbacks = 0          # counted across resumes
         self._last_take = 0          # `iterations` at the last take (at the start of the run, before the first)
         self._unrecorded = False          # a restored state that the statistics have not seen yet
@@ -276,9 +306,24 @@ class Trainer:
         return files + [path]
 
     def resume(self):
-        """Continue from what save_state() left in `out`."""
-        state = torch.load(os.path.join(self.out, STATE_FILE), map_location="cpu", weights_only=True)
-        load_checkpoint(self.out, self.gen, self.dis, self.step.gen_opt, self.step.dis_opt)
+        """Continue from what save_state() left in `out` - or, with a spill, from the newer of that and the last valid spill file."""
+        path = os.path.join(self.out, STATE_FILE)
+        found = None
+        if self.spill is not None:
+            from .spill import SnapshotSpill, restore_training_state
+            found = SnapshotSpill.latest(self.spill.folder)
+        if found is None or os.path.exists(path):
+            state = torch.load(path, map_location="cpu", weights_only=True)
+            if found is not None and int(found.host_state["iterations"]) <= int(state["iterations"]):
+                found = None
+        if found is not None:
+            restore_training_state(found, self.step, self.average)
+            state = found.host_state
+        else:
+            load_checkpoint(self.out, self.gen, self.dis, self.step.gen_opt, self.step.dis_opt)
+        if self.spill is not None:
+            _write_json(os.path.join(self.out, "error", "resumes.json"),
+                        {"from": "spill" if found is not None else "save", "iterations": int(state["iterations"])})
         self.epoch, self.sub, self.i, self.iterations = (int(state[k]) for k in ("epoch", "sub", "i", "iterations"))
         self.pipeline.load_state_dict(state["pipeline"])
         noise = state["fixed_noise"]
@@ -287,7 +332,7 @@ class Trainer:
         self.sampler.fixed_noise.copy_(noise)
         self._latent_gen.set_state(state["latent_state"])
         self.history.load_state_dict(state["history"])
-        if self.average is not None:
+        if self.average is not None and found is None:          # a spill's average went in with its tensors
             if "average" in state:
                 self.average.load_state_dict(state["average"])
             else:
@@ -298,7 +343,23 @@ class Trainer:
         if self.snapshot is not None:
             self.rollbacks = int(state.get("rollbacks", 0))
         self._last_take = self.iterations          # no committed slot yet: the first take is rollback_every iterations away
+        self._last_spill = self.iterations
         return self
+
+    def _spill_host_state(self):
+        """what save_state() puts into trainer.torch and netG.extra.torch, as of now: the host state of a take that may be spilled"""
+        if self._fixed_noise_host is None:
+            self._fixed_noise_host = self.sampler.fixed_noise.detach().cpu()          # constant during a run
+        uv = [p.requires_grad for n, p in self.dis.named_parameters() if n.endswith(("weight_u", "weight_v"))]
+        state = {"epoch": self.epoch, "sub": self.sub, "i": self.i, "iterations": self.iterations,
+                 "pipeline": self.pipeline.state_dict(), "fixed_noise": self._fixed_noise_host,
+                 "latent_state": self._latent_gen.get_state(), "history": self.history.state_dict(),
+                 "rollbacks": int(self.rollbacks), "noise": self._noise_host, "dis_uv_trainable": bool(uv) and all(uv)}
+        if self.average is not None:
+            state["average"] = {"updates": int(self.average.updates), "one_minus_beta": float(self.average.one_minus_beta)}
+        if self._guards():
+            state["guard"] = {tag: opt.counters_state() for tag, opt in self._guards()}
+        return state
 
     def _guards(self):
         """[("G" | "D", optimizer)] of the optimizers that keep guard counters"""
@@ -402,8 +463,16 @@ class Trainer:
         pairs = self.history.flush()          # the one host read of the losses
         before = self.rollbacks
         self._checks()
+        if self.spill is not None and self.rollbacks == before and self.iterations - self._last_spill >= self.spill_every:
+            if self.spill.begin():          # the slot committed at an earlier progress line; this stream only records an event
+                self._last_spill = self.iterations
         if self.snapshot is not None and self.rollbacks == before and self.iterations - self._last_take >= self.rollback_every:
-            self.snapshot.take(self.iterations)          # two launches on this stream, no host read; commits itself if finite
+            # two launches on this stream, no host read; commits itself if finite.  With a spill the take's host state goes with it:
+            # host values, and the guards' counters read once more (64 bytes each, at a line that reads from the device anyway)
+            if self.spill is not None:
+                self.spill.take(self.iterations, self._spill_host_state())
+            else:
+                self.snapshot.take(self.iterations)
             self._last_take = self.iterations
         if self.log is None or not (self.history.d and self.history.g):
             return
@@ -437,6 +506,13 @@ class Trainer:
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
         returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
+        try:
+            return self._run()
+        finally:
+            if self.spill is not None:
+                self.spill.wait()          # no half-started writer is left behind, whether the run returns or raises
+
+    def _run(self):
         batches = self.pipeline.batches_per_epoch
         while self.epochs is None or self.epoch < self.epochs:
             e = self.epoch
@@ -522,6 +598,9 @@ def main(argv=None):
                          "one, and return to it instead of stopping on a NaN or an exhausted guard (OUT/error/rollbacks.json); needs "
                          "--stats-every or a guarded optimizer; 0: off")
     ap.add_argument("--max-rollbacks", type=int, default=3, metavar="N", help="stop as without --rollback-every after N rollbacks")
+    ap.add_argument("--spill-every", type=int, default=0, metavar="N",
+                    help="write the last-good copy to OUT/spill in the background once N iterations lie behind the last one, and let "
+                         "--resume continue from it when it is newer than the last save; needs --rollback-every; 0: off")
     args = ap.parse_args(argv)
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
@@ -531,6 +610,10 @@ def main(argv=None):
         ap.error("--max-consecutive-skips must be >= 1")
     if args.rollback_every < 0 or args.max_rollbacks < 0:
         ap.error("--rollback-every and --max-rollbacks must be >= 0")
+    if args.spill_every < 0:
+        ap.error("--spill-every must be >= 0")
+    if args.spill_every > 0 and args.rollback_every <= 0:
+        ap.error("--spill-every needs --rollback-every: what goes to disk is the last-good copy")
     guarded_step = args.clip_grad_norm is not None or args.no_skip_nonfinite
     if args.rollback_every > 0 and not (args.stats_every > 0 or guarded_step):
         ap.error("--rollback-every needs --stats-every or a guarded optimizer (--clip-grad-norm / --no-skip-nonfinite): "
@@ -580,7 +663,7 @@ def main(argv=None):
     trainer = Trainer(step, pipeline, args.out, epochs=args.epochs, max_iterations=args.max_iterations, images=args.images,
                       seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average, stats=stats,
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
-                      snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks,
+                      snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()

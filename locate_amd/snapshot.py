@@ -21,7 +21,8 @@ Limits:
     fails again after the rollback, and the trainer stops, as it always did, once `max_rollbacks` is used up;
   * data parallelism is out of scope - every rank would have to take the same decision: `TrainingSnapshot` over a step with a
     gradient reducer raises ValueError;
-  * a slot lives in device memory only; persisting it is what the checkpoint files are for.
+  * a slot lives in device memory only; `locate_amd.spill.SnapshotSpill` writes a committed slot to disk in the background, and
+    the checkpoint files persist the state at the end of an epoch.
 
 Importing this module does not load the HIP library.  A tensor on the CPU raises TypeError: there is no CPU path."""
 import ctypes
