@@ -306,14 +306,14 @@ __global__ void __launch_bounds__(256, (WGM * TM > 4 ? 2 : 3)) conv_wgrad_bx6_ke
     float g_scale = 1.0f, x_scale = 1.0f, g_unscale = 1.0f, x_unscale = 1.0f;
     if constexpr (NP == 2) {
         const float gmax = __uint_as_float(absmax_read(p.g_absmax)) * fmaxf(fmaxf(gs0, gs1), fmaxf(gs2, gs3));
-        const int kg_ = f16_scale_exp(__float_as_uint(gmax) + (p.gscale_bg > 0 ? 0x00800000u : 0u));    // (product rounded: one binade of slack)
+        const int kg_ = f16_scale_exp(__float_as_uint(gmax), p.gscale_bg > 0 ? 1u : 0u);    // (product rounded: one binade of slack)
         const int kx_ = f16_scale_exp(absmax_read(p.x_absmax));
         g_scale = pow2f(kg_); x_scale = pow2f(kx_);
         unscale_pair(kg_, kx_, g_unscale, x_unscale);
     }
     if constexpr (NP == 4) {
         const float gmax = __uint_as_float(absmax_read(p.g_absmax)) * fmaxf(fmaxf(gs0, gs1), fmaxf(gs2, gs3));
-        const int kg_ = f8_scale_exp(__float_as_uint(gmax) + (p.gscale_bg > 0 ? 0x00800000u : 0u));
+        const int kg_ = f8_scale_exp(__float_as_uint(gmax), p.gscale_bg > 0 ? 1u : 0u);
         const int kx_ = f8_scale_exp(absmax_read(p.x_absmax));
         g_scale = pow2f(kg_); x_scale = pow2f(kx_);
         unscale_pair(kg_, kx_, g_unscale, x_unscale);

@@ -321,6 +321,17 @@ __global__ void __launch_bounds__(256) gate_fwd_stats_kernel(const float* __rest
     }
 }
 
+// da of one plane under a gamma that is not finite.  The reference multiplies every x*g by gamma BEFORE it sums the plane
+// (merge.py:33-38 on the expanded a): terms of both signs, or a zero, make the sum NaN where gamma * (sum x*g) is an Inf.  One lane
+// walks the plane - the run is lost either way, only the class has to be the reference's; a finite gamma never comes here.  Out of
+// line: inlined, the loop's registers cost gate_bwd_plane_kernel<1> one wave per SIMD (66 registers for 64).
+__device__ __noinline__ float gate_plane_da_nonfinite(const float* __restrict__ x, const float* __restrict__ g, int hw, float gm) {
+    float s = 0.0f;
+    for (int i = 0; i < hw; ++i) s += (x[i] * g[i]) * gm;
+    return s;
+}
+__device__ __forceinline__ bool gate_gamma_finite(float gm) { return fabsf(gm) <= 3.402823466e38f; }
+
 // dx, da (full, or gamma * sum x*g per plane in broadcast mode) and, per BLOCK, the sum of x^2*g over the planes the
 // block visited (fixed order: deterministic).  WPP waves share a plane: 1 for small planes (one wave per plane),
 // 4 (the whole block) for planes of >= 1024 elements, 16-byte accesses when hw % 4 == 0.
@@ -385,14 +396,16 @@ __global__ void __launch_bounds__(256) gate_bwd_plane_kernel(const float* __rest
         const double s2 = wave_sum_d((double)sx2g);      // dgamma sums x^2 g with heavy cancellation: leave fp32 early
         if (WPP == 1) {
             wacc += s2;
-            if (lane == 0 && a_per_plane) da_plane[p] = gm * sxg;
+            if (lane == 0 && a_per_plane) da_plane[p] = gate_gamma_finite(gm) ? gm * sxg : gate_plane_da_nonfinite(x + base, g + base, hw, gm);
         } else {
             __syncthreads();
             if (lane == 0) { pxg[wid] = sxg; px2g[wid] = s2; }
             __syncthreads();
             if (threadIdx.x == 0) {
                 wacc += (px2g[0] + px2g[1]) + (px2g[2] + px2g[3]);
-                if (a_per_plane) da_plane[p] = gm * ((pxg[0] + pxg[1]) + (pxg[2] + pxg[3]));
+                if (a_per_plane)
+                    da_plane[p] = gate_gamma_finite(gm) ? gm * ((pxg[0] + pxg[1]) + (pxg[2] + pxg[3]))
+                                                        : gate_plane_da_nonfinite(x + base, g + base, hw, gm);
             }
         }
     }
@@ -463,7 +476,7 @@ __global__ void __launch_bounds__(256) gate_bwd_small_kernel(const float* __rest
         }
         if (live && li == 0) {
             wacc += s2;
-            if (a_per_plane) da_plane[p] = gm * sxg;
+            if (a_per_plane) da_plane[p] = gate_gamma_finite(gm) ? gm * sxg : gate_plane_da_nonfinite(x + p * hw, g + p * hw, hw, gm);
         }
     }
     wacc = wave_sum_d(wacc);          // the plane leaders' sums (other lanes hold 0), fixed order

@@ -165,19 +165,20 @@ __device__ __forceinline__ size_t panel_split_offset_dev(int rows, int ld) { ret
 // 2^k and 2^-k are normal fp32 numbers (pow2f: |k| <= 126).  k = 14 - e runs from -113 (largest finite fp32 binade) upwards, so
 // the clamp only ever binds at +126, for tensors whose largest magnitude is below 2^-112: their pieces merely sit lower in
 // fp16's range.  (A tighter clamp, at +-100 say, would leave tensors of >= 2^115 scaled to >= 2^15: high pieces of inf.)
-__host__ __device__ __forceinline__ int f16_scale_exp(unsigned bits) {
-    const int e = (int)((bits >> 23) & 0xffu) - 127;
-    if (e == -127) return 0;
-    const int k = 14 - e;
+// A largest magnitude that is not finite (the words keep an Inf; fmaxf drops a NaN): k = 0, no scaling.  With k = 14 - 128 every
+// finite element of the tensor would be scaled to an fp16 zero - finite zeros in outputs the Inf never touches; unscaled, the Inf
+// saturates its own pieces and the other elements keep their values (as well as unscaled fp16 pieces hold them).
+// `grown`: 1 where the word is a product still to be rounded - one binade of slack, taken from a finite word only.
+__host__ __device__ __forceinline__ int scale_exp_below(int top, unsigned bits, unsigned grown) {
+    const unsigned field = (bits >> 23) & 0xffu;
+    // zero / denormal (field 0, without slack) and not finite (field 255): one unsigned comparison, field - 1 wraps for 0
+    if (grown == 0u ? field - 1u >= 254u : field == 255u) return 0;
+    const int k = top - ((int)(field + grown) - 127);
     return k > 126 ? 126 : (k < -126 ? -126 : k);
 }
-// the same for e4m3 operands (largest finite value 448): absmax * 2^k in [2^7, 2^8)
-__host__ __device__ __forceinline__ int f8_scale_exp(unsigned bits) {
-    const int e = (int)((bits >> 23) & 0xffu) - 127;
-    if (e == -127) return 0;
-    const int k = 7 - e;
-    return k > 126 ? 126 : (k < -126 ? -126 : k);          // (binds below 2^-119 only, see f16_scale_exp)
-}
+__host__ __device__ __forceinline__ int f16_scale_exp(unsigned bits, unsigned grown = 0u) { return scale_exp_below(14, bits, grown); }
+// the same for e4m3 operands (largest finite value 448): absmax * 2^k in [2^7, 2^8)   (the clamp binds below 2^-119 only)
+__host__ __device__ __forceinline__ int f8_scale_exp(unsigned bits, unsigned grown = 0u) { return scale_exp_below(7, bits, grown); }
 __device__ __forceinline__ float pow2f(int k) { return __uint_as_float((unsigned)(k + 127) << 23); }      // -126 <= k <= 127
 // The inverse of two operand scales 2^ka, 2^kb as two factors applied one after the other, acc = (acc * u1) * u2: 2^-(ka + kb)
 // need not be a normal fp32 number, and neither need acc * 2^-ka be (a gradient of 2^118 against activations of 2^3: the

@@ -8,13 +8,17 @@
 // clamp(min=0) passes the gradient where its argument is >= 0 (ATen clamp backward mask).
 #include "common.h"
 
+// clamp(v, min=0) as ATen computes it: a NaN argument stays NaN (fmaxf would return the 0 and a NaN discriminator output would
+// leave the printed loss finite); its gradient mask (v >= 0) is false there, as ATen's.
+__device__ __forceinline__ float hinge_clamp(float v) { return v < 0.0f ? 0.0f : v; }
+
 __global__ void __launch_bounds__(256) d_loss_kernel(const float* __restrict__ t, const float* __restrict__ f,
                                                      const float* __restrict__ a, int B, float gamma, float* __restrict__ losses,
                                                      float* __restrict__ gt, float* __restrict__ gf, float* __restrict__ ga) {
     __shared__ double scratch[16];
     double hs = 0.0, ts = 0.0, as = 0.0;
     for (int i = threadIdx.x; i < B; i += blockDim.x) {
-        hs += (double)fmaxf(1.0f - t[i], 0.0f) + (double)fmaxf(1.0f + f[i], 0.0f);
+        hs += (double)hinge_clamp(1.0f - t[i]) + (double)hinge_clamp(1.0f + f[i]);
         ts += t[i];
         as += a[i];
     }
@@ -44,7 +48,7 @@ __global__ void __launch_bounds__(256) g_loss_kernel(const float* __restrict__ f
     double hs = 0.0;
     const float invB = 1.0f / (float)B;
     for (int i = threadIdx.x; i < B; i += blockDim.x) {
-        hs += (double)fmaxf(1.0f - f[i], 0.0f);
+        hs += (double)hinge_clamp(1.0f - f[i]);
         gf[i] = (1.0f - f[i]) >= 0.0f ? -invB : 0.0f;
     }
     hs = block_sum<double>(hs, scratch);

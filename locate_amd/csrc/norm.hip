@@ -197,6 +197,27 @@ __device__ __forceinline__ float norm_go(float xv, float gv, float mu, float inv
     return roottanh_grad_f(o, gv);
 }
 
+// y[p] * (S1[p], S2[p]) under a scale y that is not finite.  The reference multiplies the scale into every element BEFORE it sums
+// (xg = y g / s and its mean; dz = -sum((x - mu) g y) / s^2): gradients of both signs under an infinite scale make those sums NaN
+// where y * S is an Inf.  One lane walks the plane - nothing is left of such a run, only the class has to be the reference's.  A
+// finite scale never comes here; where the plane sums are not finite themselves (always so with the fused activation, whose
+// derivative at an infinite argument is NaN) the product already is what it has to be.
+__device__ __forceinline__ bool norm_scale_special(float y, float s1, float s2) {
+    const float big = 3.402823466e38f;
+    return !(fabsf(y) <= big) && fabsf(s1) <= big && fabsf(s2) <= big;
+}
+// Inline: the loop runs after the plane's reductions, where the hot loop's registers are free again - no kernel crosses an
+// occupancy step (out of line, the call's clobbers take norm_bwd_plane_kernel<false> from 64 registers to 66).
+__device__ __forceinline__ float2 norm_scaled_plane_sums(const float* __restrict__ x, const float* __restrict__ g, int hw, float mu, float y) {
+    float sa = 0.0f, sb = 0.0f;
+    for (int i = 0; i < hw; ++i) {
+        const float gv = g[i];
+        sa += y * gv;
+        sb += ((x[i] - mu) * gv) * y;
+    }
+    return make_float2(sa, sb);
+}
+
 template <bool ACT>
 __global__ void __launch_bounds__(256) norm_bwd_plane_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                              const float* __restrict__ stats, const float* __restrict__ scale,
@@ -247,11 +268,14 @@ __global__ void __launch_bounds__(256) norm_bwd_plane_kernel(const float* __rest
             S2[p] = s2;
             if (block_partial) {
                 const float yv = scale[scale_per_sample ? p : c];
+                double ya = (double)yv * (double)s1, yb = (double)yv * (double)s2;
+                if constexpr (!ACT)
+                    if (norm_scale_special(yv, s1, s2)) { const float2 t = norm_scaled_plane_sums(x + base, g + base, hw, mu, yv); ya = (double)t.x; yb = (double)t.y; }
 #pragma unroll
                 for (int q = 0; q < NORM_MAX_GROUPS; ++q)
                     if (q == grp) {
-                        acc_a[q] += (double)yv * (double)s1;
-                        acc_b[q] += (double)yv * (double)s2;
+                        acc_a[q] += ya;
+                        acc_b[q] += yb;
                     }
                 if (dscale_sample) dscale_sample[p] = s2 / stats[2 * grp + 1];
             }
@@ -328,11 +352,14 @@ __global__ void __launch_bounds__(256) norm_bwd_plane_small_kernel(const float* 
             S1[p] = s1;
             S2[p] = s2;
             if (block_partial) {
+                double ya = (double)yv * (double)s1, yb = (double)yv * (double)s2;
+                if constexpr (!ACT)
+                    if (norm_scale_special(yv, s1, s2)) { const float2 t = norm_scaled_plane_sums(x + p * hw, g + p * hw, hw, mu, yv); ya = (double)t.x; yb = (double)t.y; }
 #pragma unroll
                 for (int q = 0; q < NORM_MAX_GROUPS; ++q)
                     if (q == grp) {
-                        acc_a[q] += (double)yv * (double)s1;
-                        acc_b[q] += (double)yv * (double)s2;
+                        acc_a[q] += ya;
+                        acc_b[q] += yb;
                     }
                 if (dscale_sample) dscale_sample[p] = s2 / sd;
             }
@@ -383,7 +410,8 @@ __global__ void __launch_bounds__(256) norm_bwd_final_kernel(const float* __rest
                                                              const float* __restrict__ stats, const float* __restrict__ scale,
                                                              int scale_per_sample, float* __restrict__ dscale,
                                                              float* __restrict__ dbias, double* __restrict__ partial, int B,
-                                                             int C, int groups) {
+                                                             int C, int groups, const float* __restrict__ x,
+                                                             const float* __restrict__ g, int hw, int with_act) {
     __shared__ double scratch[16];
     __shared__ float part_b[256], part_y[256];
     const int Bg = B / groups;
@@ -403,11 +431,17 @@ __global__ void __launch_bounds__(256) norm_bwd_final_kernel(const float* __rest
             db += s1;
             if (scale_per_sample) dscale[p] = s2 / sf;
             else dy += s2 / sf;
+            double ya = (double)y * (double)s1, yb = (double)y * (double)s2;
+            // (never with the fused activation: S1, S2 are sums of g * RootTanh'(out) there, not of g)
+            if (!with_act && norm_scale_special(y, s1, s2)) {
+                const float2 t = norm_scaled_plane_sums(x + p * hw, g + p * hw, hw, stats[2 * grp], y);
+                ya = (double)t.x; yb = (double)t.y;
+            }
 #pragma unroll
-            for (int g = 0; g < NORM_MAX_GROUPS; ++g)
-                if (g == grp) {
-                    sum_yg[g] += (double)y * (double)s1;
-                    sum_yxg[g] += (double)y * (double)s2;
+            for (int q = 0; q < NORM_MAX_GROUPS; ++q)
+                if (q == grp) {
+                    sum_yg[q] += ya;
+                    sum_yxg[q] += yb;
                 }
         }
     }
@@ -529,7 +563,7 @@ LOCATE_API int locate_norm_bwd(const float* x, const float* g, const float* stat
     else
         norm_bwd_plane_kernel<false><<<(int)blocks, 256, 0, st>>>(x, g, stats, scale, scale_per_sample, bias, C, S1, S2, planes, planes_g, hw, nullptr, nullptr);
     LOCATE_LAUNCH_CHECK("locate_norm_bwd(plane)");
-    norm_bwd_final_kernel<<<nfb, 256, 0, st>>>(S1, S2, stats, scale, scale_per_sample, dscale, dbias, partial, B, C, groups);
+    norm_bwd_final_kernel<<<nfb, 256, 0, st>>>(S1, S2, stats, scale, scale_per_sample, dscale, dbias, partial, B, C, groups, x, g, hw, with_act);
     LOCATE_LAUNCH_CHECK("locate_norm_bwd(final)");
     const dim3 grid(stream_grid(planes_g * hw, 1024), groups);
     if (with_act)

@@ -201,6 +201,22 @@ __global__ void __launch_bounds__(256) upsample2x_bwd_kernel(const float* __rest
             }
             acc = fmaf(wy[a], row, acc);
         }
+        // ATen's scatter also sends output row 0 to input row min(1, H - 1) (and column 0 likewise) with the clamped source's
+        // weight l1 = 0: nothing for a finite gradient, a NaN for a NaN or an Inf.  The footprint of a special is ATen's.
+        const int ty = H > 1 ? 1 : 0, tx = W > 1 ? 1 : 0;
+        if (iy == ty || ix == tx) {
+            if (iy == ty) {
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if (wx[b] != 0.0f) acc = fmaf(0.0f, gp[2 * ix - 1 + b], acc);
+                if (ix == tx) acc = fmaf(0.0f, gp[0], acc);
+            }
+            if (ix == tx) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+                    if (wy[a] != 0.0f) acc = fmaf(0.0f, gp[(2 * iy - 1 + a) * OW], acc);
+            }
+        }
         if (POOL) {          // feature_pool_bwd_kernel's values: g * (1 / 2) to both raw elements, added to what is there on request
             float2* dst = reinterpret_cast<float2*>(gx) + i;
             const float o = acc * 0.5f;
@@ -245,6 +261,19 @@ __global__ void __launch_bounds__(256) upsample2x_bwd_vec_kernel(const float* __
                 wx[e][k] = (ox >= 0 && ox < OW) ? bil_weight_to(ox, W, ix0 + e) : 0.0f;
             }
         const bool has_left = c0 > 0, has_right = c0 + 8 < OW;
+        // The zero-weight terms of ATen's scatter (see upsample2x_bwd_kernel): output row 0 into input row min(1, H - 1) and output
+        // column 0 into input column 1 (W is a multiple of 4, so column 1 exists: element 1 of the row's first thread).  Row 0 is
+        // loaded here, ahead of the four rows of the stencil, by the threads of that one input row; column 0 is element v[1] of
+        // the rows the first thread loads anyway.
+        const bool zero_row = iy == (H > 1 ? 1 : 0), first = j == 0;
+        float4 z1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), z2 = z1;
+        float zl = 0.0f, zr = 0.0f;
+        if (zero_row) {
+            z1 = *reinterpret_cast<const float4*>(gp + c0);
+            z2 = *reinterpret_cast<const float4*>(gp + c0 + 4);
+            if (has_left) zl = gp[c0 - 1];
+            if (has_right) zr = gp[c0 + 8];
+        }
         float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -263,6 +292,16 @@ __global__ void __launch_bounds__(256) upsample2x_bwd_vec_kernel(const float* __
                     if (wx[e][b] != 0.0f) row = fmaf(wx[e][b], v[2 * e + b], row);
                 acc[e] = fmaf(wy[a], row, acc[e]);
             }
+            acc[1] = fmaf(0.0f, first ? v[1] : 0.0f, acc[1]);
+        }
+        if (zero_row) {
+            const float v[10] = {zl, z1.x, z1.y, z1.z, z1.w, z2.x, z2.y, z2.z, z2.w, zr};
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    if (wx[e][b] != 0.0f) acc[e] = fmaf(0.0f, v[2 * e + b], acc[e]);
+            acc[1] = fmaf(0.0f, first ? v[1] : 0.0f, acc[1]);
         }
         if (POOL) {
             float4* dst = reinterpret_cast<float4*>(gx) + 2 * (int64_t)i;
