@@ -447,6 +447,35 @@ int locate_digest_chunk_elems(void);
 int locate_digest(const void* records, const void* chunks, const void* first, int n_tensors, int n_chunks, void* partials, void* out,
                   void* stream);
 
+/* ---- per-tensor deltas against a base copy (no reference counterpart; locate_amd/dynamics.py), every tensor of a table in one
+ *      pass over memory.  tensors: DEVICE array of {const float* w; float* base; int64 n; int32 first_chunk; int32 pad} records
+ *      (locate_dyn_tensor_record_bytes() = 32): w the live tensor, base its n-element slot in an arena the caller owns; chunks:
+ *      DEVICE (tensor index, chunk index) int pairs in pieces of locate_dyn_chunk_elems(), a tensor's chunks consecutive and in
+ *      ascending order, its chunk 0 at position first_chunk of the array.  With d[i] = w[i] - base[i] (one fp32 subtraction,
+ *      denormals kept), records: n_tensors records (locate_dyn_record_bytes() = 32), 8-byte aligned:
+ *        double delta_sumsq   sum of (double) d * (double) d over the FINITE d (exact squares; within n * 2^-52 relative)
+ *        double base_sumsq    the same sum over the finite base[i]
+ *        uint32 delta_absmax  bit pattern of the largest finite |d|, 0 if there is none
+ *        uint32 unchanged     elements with w[i] == base[i] compared as fp32 (+0 == -0 counts, a NaN never does), modulo 2^32
+ *        uint32 nonfinite     elements whose d is NaN or +-Inf (left out of the two delta fields), modulo 2^32
+ *        uint32 pad           0
+ *      mode 1 (record): writes records and workspace, only reads base.  mode 2 (rebase): base[i] = w[i] bit for bit, NaN
+ *      payloads included; no record: records and workspace may be NULL.  mode 3: both in one pass; the records describe the base
+ *      as it was.  workspace: locate_dyn_workspace_bytes(n_chunks) bytes, 8-byte aligned, need not be zeroed.
+ *      A tensor's record depends only on its contents and n - not on the table around it, its position, the alignment of w or
+ *      base (4 bytes are enough; 16-byte loads and stores are used where a chunk of both is 16-byte aligned) or the grid: two
+ *      calls give the same bits.  No floating-point atomics.  A table entry that is out of range or inconsistent is skipped:
+ *      its record is then unspecified, and nothing is written through it.  One launch (rebase) or two; no allocation, host
+ *      read or synchronisation: legal under stream capture.  At most locate_dyn_max_blocks() blocks stride over the chunk
+ *      table. ---- */
+size_t locate_dyn_tensor_record_bytes(void);
+size_t locate_dyn_record_bytes(void);
+int locate_dyn_chunk_elems(void);
+int locate_dyn_max_blocks(void);
+size_t locate_dyn_workspace_bytes(int n_chunks);
+int locate_dyn_pass(const void* tensors, const void* chunks, int n_tensors, int n_chunks, int mode, void* records, void* workspace,
+                    void* stream);
+
 /* ---- loss glue (main.py:149-156,164-169, libs/utils.py:133-134, libs/grad_penalty.py:1-2): values and the
  *      gradients w.r.t. the discriminator outputs ---- */
 int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, float* losses,

@@ -144,6 +144,12 @@ PROTOTYPES = {
     "locate_digest_record_bytes": (c_sz, []),
     "locate_digest_chunk_elems": (c_i, []),
     "locate_digest": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
+    "locate_dyn_tensor_record_bytes": (c_sz, []),
+    "locate_dyn_record_bytes": (c_sz, []),
+    "locate_dyn_chunk_elems": (c_i, []),
+    "locate_dyn_max_blocks": (c_i, []),
+    "locate_dyn_workspace_bytes": (c_sz, [c_i]),
+    "locate_dyn_pass": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     "locate_d_loss": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "locate_g_loss": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "locate_input_param_record_bytes": (c_sz, []),
@@ -169,7 +175,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 13
+EXPECTED_ABI = 14
 
 
 _lib = None

@@ -4,7 +4,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
 
     python -m locate_amd.run --store FILE.npy --image-size S --batch B --out DIR [--epochs N] [--max-iterations N]
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
-                             [--swd-images 0] [--ema-half-life 0] [--stats-every 0]
+                             [--swd-images 0] [--ema-half-life 0] [--stats-every 0] [--dynamics-every 0]
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
                              [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0]
 
@@ -32,6 +32,9 @@ Differences from the reference, all additions:
     (`locate_amd.stats`) - is taken by a launch beside the training step; `OUT/error/{epoch}-stats.npz` holds an epoch's records.
     The records are checked wherever the losses are read and immediately before every save: a run that holds a NaN or an Inf
     stops with `NonFiniteError`, writes `OUT/error/nonfinite.json` and leaves the files of the last good save as they are;
+  * `dynamics=` / `--dynamics-every N` (off by default): around every N-th iteration, per tensor the update-to-weight ratio
+    |dw| / |w| of that one iteration and per spectrally normalised layer the sigma its forward divides by beside its top singular
+    value (`locate_amd.dynamics`), by launches beside the training step; `OUT/error/{epoch}-dynamics.npz` holds an epoch's records;
   * `--clip-grad-norm X` / `--no-skip-nonfinite` (without either, nothing below happens): both networks are stepped by
     `GuardedNadam` (`locate_amd.guard`) instead of `Nadam`: a step whose gradients hold a NaN or an Inf is skipped on the device
     (unless `--no-skip-nonfinite`), and with X > 0 the gradients are scaled down to the global norm X.  `OUT/error/{epoch}-guard.json`
@@ -146,6 +149,19 @@ class Trainer:
     epoch taken by this call of run(); the records start empty in every epoch, like the curves.  Under data parallelism only
     rank 0 needs one: the weights, and the gradients after the exchange, are equal on every rank.
 
+    dynamics: a `RunDynamics` over step.gen and step.dis, or None (the default: nothing below happens, and every file, record and
+    key is what it is without this argument); `dynamics_every`: N >= 0, 0 (the default) is off.  `dynamics.mark()` is issued before
+    the iteration that makes `iterations` a multiple of N and `dynamics.record(iterations)` after it - behind `average.update()`
+    and the statistics' record, on the same stream - so a record's delta is exactly what that one iteration (its D step and its G
+    step) did to the weights, and the cost falls on every N-th iteration only.  Both only read what the training owns.
+    `out/error/{e+1}-dynamics.npz` (`RunDynamics.save`) is written beside `{e+1}-stats.npz` and holds the records of that epoch
+    taken by this call of run(); the records start empty in every epoch.  Nothing goes into trainer.torch: after a resume the top
+    singular vectors start again from the live u / v and the file holds the records since the resume, as with the statistics.
+    An iteration that does not step a network's optimizer (miniter > 1: the generator is stepped every miniter-th iteration) shows
+    `unchanged == n` for that network's weights.  After a rollback the next record is simply taken on the restored weights.  With
+    graphed=True the iteration that builds the graphs runs its two warm-up iterations too: a record around it spans all three.
+    Under data parallelism only rank 0 needs one.
+
     Guarded optimizers: where step.gen_opt or step.dis_opt is a `GuardedNadam` (anything with `counters()`; with plain `Nadam`s
     nothing below happens, and every file, record and key is what it is today), its counters are read where this loop reads from
     the device anyway - with the progress line - and before every save_state().  An optimizer whose `consecutive_skips` has reached
@@ -188,7 +204,7 @@ class Trainer:
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
-                 max_rollbacks=3, spill_every=0):
+                 max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -225,6 +241,9 @@ class Trainer:
         if int(stats_every) < 0:
             raise ValueError("stats_every must be >= 0, got %r" % (stats_every,))
         self.stats, self.stats_every = stats, int(stats_every)
+        if int(dynamics_every) < 0:
+            raise ValueError("dynamics_every must be >= 0, got %r" % (dynamics_every,))
+        self.dynamics, self.dynamics_every = dynamics, int(dynamics_every)
         if int(max_consecutive_skips) < 1:
             raise ValueError("max_consecutive_skips must be >= 1, got %r" % (max_consecutive_skips,))
         self.max_consecutive_skips = int(max_consecutive_skips)
@@ -527,6 +546,9 @@ class Trainer:
                         self._checks(before_save=True)
                         self.written += self.save_state()
                         return self.iterations
+                    followed = self.dynamics is not None and self.dynamics_every and (self.iterations + 1) % self.dynamics_every == 0
+                    if followed:
+                        self.dynamics.mark()          # one launch on this stream: the base this iteration's delta is taken from
                     out = self._iteration()
                     if self.average is not None:
                         self.average.update()          # one launch on this stream, behind the iteration's last write
@@ -534,6 +556,8 @@ class Trainer:
                     self.iterations += 1
                     if self.stats is not None and self.stats_every and self.iterations % self.stats_every == 0:
                         self._record_stats()
+                    if followed:
+                        self.dynamics.record(self.iterations)          # no host read
                     i = self.i
                     if i % miniter == 0:          # main.py:158
                         self.history.record(out)
@@ -550,8 +574,11 @@ class Trainer:
             if self.stats is not None:
                 self.written += self.stats.save(os.path.join(self.out, "error"), e + 1)
                 self.stats.clear()
+            if self.dynamics is not None and self.dynamics_every:
+                self.written += self.dynamics.save(os.path.join(self.out, "error"), e + 1)
+                self.dynamics.clear()
             if self._guards():
-                self.written.append(self._save_guards(e + 1))          # raises, before the save below, if a guard is exhausted
+                self.written.append(self._save_guards(e + 1))         # raises, before the save below, if a guard is exhausted
             if self.swd is not None:
                 self.written.append(self._measure(e))
             self.epoch, self.sub = e + 1, 0
@@ -586,6 +613,9 @@ def main(argv=None):
     ap.add_argument("--stats-every", type=int, default=0, metavar="N",
                     help="after every N-th iteration, record per-tensor weight and gradient statistics (OUT/error/EPOCH-stats.npz) "
                          "and stop with an error, before anything is saved, once a weight or gradient is NaN or Inf; 0: off")
+    ap.add_argument("--dynamics-every", type=int, default=0, metavar="N",
+                    help="around every N-th iteration, record per-tensor update-to-weight ratios and per-layer spectral norms "
+                         "(OUT/error/EPOCH-dynamics.npz); 0: off")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="step both networks with GuardedNadam and scale the gradients down to the global L2 norm X where theirs is "
                          "larger (OUT/error/EPOCH-guard.json holds the counters); 0: guard without clipping")
@@ -604,6 +634,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
+    if args.dynamics_every < 0:
+        ap.error("--dynamics-every must be >= 0")
     if args.clip_grad_norm is not None and not (0.0 <= args.clip_grad_norm < float("inf")):
         ap.error("--clip-grad-norm must be finite and >= 0")
     if args.max_consecutive_skips < 1:
@@ -656,6 +688,10 @@ def main(argv=None):
     if args.stats_every > 0:
         from .stats import RunStatistics
         stats = RunStatistics(gen, dis)
+    dynamics = None
+    if args.dynamics_every > 0:
+        from .dynamics import RunDynamics
+        dynamics = RunDynamics(gen, dis)
     snapshot = None
     if args.rollback_every > 0:
         from .snapshot import TrainingSnapshot
@@ -664,6 +700,7 @@ def main(argv=None):
                       seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average, stats=stats,
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
+                      dynamics=dynamics, dynamics_every=args.dynamics_every,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
