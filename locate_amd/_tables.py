@@ -1,6 +1,7 @@
 """Host side of the kernels driven by a device chunk table (csrc/multitensor.h): the Nadam step, the guard, the averaged
-generator, the run statistics and the gradient bucket copies.  Each packs its own records; the (tensor, chunk) list, the staging
-and the bounded cache are here.  Importing this module does not load the HIP library."""
+generator, the run statistics and dynamics, the snapshot, the digest and the gradient bucket copies.  Each packs its own records;
+the (tensor, chunk) list, the staging, the bounded cache, the check of the arguments and the layout of an arena are here.
+Importing this module does not load the HIP library."""
 from collections import namedtuple
 
 import torch
@@ -37,3 +38,25 @@ def remember(cache, key, table, bound):
         cache.clear()
     cache[key] = table
     return table
+
+
+def require_device_tensors(tensors, what):
+    for t in tensors:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise TypeError("%s computes on the GPU only; got %s" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("%s takes contiguous float32 tensors, got %s%s" % (what, t.dtype, "" if t.is_contiguous() else " (strided)"))
+
+
+def arena_layout(word_counts):
+    """(byte offset of every tensor in a slot, slot_bytes) for tensors of `word_counts` 4-byte words: in order, every offset a
+    multiple of 16, a zero-length tensor takes no space."""
+    offsets, at = [], 0
+    for n in word_counts:
+        n = int(n)
+        if n < 0:
+            raise ValueError("a tensor of %d words" % n)
+        offsets.append(at)
+        at += (4 * n + 15) // 16 * 16
+    return offsets, at
+

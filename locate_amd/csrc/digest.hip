@@ -8,17 +8,16 @@
 // side stream and compares the result with the same sums taken on the host from the bytes that arrived there; like the
 // statistics and the snapshot it only READS what the step left and runs BETWEEN two iterations.  The reference has nothing of the kind.
 //
-// Two launches, the shape of stats.hip on the chunk-table layer of multitensor.h.  (1) digest_partial_kernel: blocks stride over
+// Two launches on the chunk-table layer of multitensor.h.  (1) digest_partial_kernel: blocks stride over
 // the int2 {tensor, chunk} list and write one {A, B} partial per entry to partials[position of the entry]; a damaged entry
 // (mt_decode false) writes a zero partial, so every word of partials[0 .. n_chunks) is written by every call.
 // (2) digest_combine_kernel: one block per tensor adds the partials of [first[t], first[t + 1]) into out[t]; a tensor without
 // chunks (n = 0) or with a damaged range gets {0, 0}.  No atomics, nothing to clear between calls.
 //
-// A bandwidth kernel (4 bytes per word): 16-byte loads between a per-word head (up to the first 16-byte boundary) and tail, as
-// guard.hip and snapshot.hip read 4-byte-aligned views; every load of a chunk is issued before the first use; at most 2048 blocks.
+// A bandwidth kernel (4 bytes per word): a chunk is read split at the 16-byte boundaries (multitensor.h's mt_read_split), every
+// load issued before the first use; the sums are multitensor.h's mt_block_total and mt_add_partials; at most 2048 blocks.
 #include "multitensor.h"
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 struct DigestTensor {          // 16 bytes
@@ -29,35 +28,15 @@ struct DigestTensor {          // 16 bytes
 struct DigestPair {            // a chunk's partial and a tensor's digest alike
     u64 a;
     u64 b;
+    __device__ __forceinline__ void add(const DigestPair& q) {
+        a += q.a;
+        b += q.b;
+    }
 };
 
 __device__ __forceinline__ void digest_take(unsigned w, unsigned index, u64& a, u64& b) {
     a += (u64)w;
     b += (u64)index * (u64)w;          // 32 x 32 -> 64, added modulo 2^64
-}
-
-// the block's total in thread 0 (other threads: unspecified); `lds` holds MT_WAVES pairs
-__device__ __forceinline__ DigestPair digest_block_reduce(u64 a, u64 b, DigestPair* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a += (u64)__shfl_xor((long long)a, o, 64);
-        b += (u64)__shfl_xor((long long)b, o, 64);
-    }
-    __syncthreads();          // lds may still be read from the previous chunk
-    if ((threadIdx.x & 63) == 0) {
-        lds[threadIdx.x >> 6].a = a;
-        lds[threadIdx.x >> 6].b = b;
-    }
-    __syncthreads();
-    DigestPair r = lds[0];
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < MT_WAVES; ++w) {
-            r.a += lds[w].a;
-            r.b += lds[w].b;
-        }
-    }
-    return r;
 }
 
 __global__ void __launch_bounds__(MT_THREADS) digest_partial_kernel(const DigestTensor* __restrict__ tensors, const int2* __restrict__ chunks,
@@ -73,18 +52,11 @@ __global__ void __launch_bounds__(MT_THREADS) digest_partial_kernel(const Digest
             continue;
         }
         const unsigned* src = T.p + begin;
-        int head = (int)((16 - (reinterpret_cast<uintptr_t>(src) & 15)) & 15) >> 2;          // words up to the first 16-byte boundary
-        head = head > len ? len : head;
-        const int n4 = (len - head) >> 2;
-        const int tail = len - head - 4 * n4;
-        u32x4 v[MT_PER_THREAD];
-#pragma unroll
-        for (int k = 0; k < MT_PER_THREAD; ++k) {
-            const int w = tid + k * MT_THREADS;
-            v[k] = w < n4 ? *reinterpret_cast<const u32x4*>(src + head + 4 * w) : u32x4{0u, 0u, 0u, 0u};
-        }
-        const unsigned h = tid < head ? src[tid] : 0u;
-        const unsigned t = tid < tail ? src[head + 4 * n4 + tid] : 0u;
+        const MtSplit sp = mt_split(src, len);
+        const int head = sp.head, n4 = sp.n4;
+        mt_word4<unsigned> v[MT_PER_THREAD];
+        unsigned h, t;
+        mt_read_split(src, sp, v, h, t);
         // word j of the chunk is word begin + j of its tensor: its factor is (begin + j + 1) mod 2^32.  A zero word adds nothing,
         // so the loads that were not taken need no branch here.
         const unsigned base = (unsigned)(begin + 1);
@@ -99,7 +71,7 @@ __global__ void __launch_bounds__(MT_THREADS) digest_partial_kernel(const Digest
         }
         digest_take(h, base + (unsigned)tid, a, b);
         digest_take(t, base + (unsigned)(head + 4 * n4 + tid), a, b);
-        const DigestPair r = digest_block_reduce(a, b, lds);
+        const DigestPair r = mt_block_total(DigestPair{a, b}, lds);
         if (tid == 0) partials[c] = r;          // c < n_chunks: inside the workspace
     }
 }
@@ -109,15 +81,9 @@ __global__ void __launch_bounds__(MT_THREADS) digest_combine_kernel(const int* _
     __shared__ DigestPair lds[MT_WAVES];
     for (int t = blockIdx.x; t < n_tensors; t += gridDim.x) {
         const int lo = first[t], hi = first[t + 1];
-        u64 a = 0ull, b = 0ull;
-        if (lo >= 0 && lo <= hi && hi <= n_chunks) {          // a damaged range reads nothing
-            for (int i = lo + (int)threadIdx.x; i < hi; i += MT_THREADS) {
-                const DigestPair q = partials[i];
-                a += q.a;
-                b += q.b;
-            }
-        }
-        const DigestPair r = digest_block_reduce(a, b, lds);
+        DigestPair r = {0ull, 0ull};
+        if (lo >= 0 && lo <= hi && hi <= n_chunks) mt_add_partials(partials + lo, hi - lo, r);          // a damaged range reads nothing
+        r = mt_block_total(r, lds);
         if (threadIdx.x == 0) out[t] = r;
     }
 }

@@ -8,24 +8,24 @@
 //   nonfinite    (uint32)   elements whose d is NaN or +-Inf; they are left out of the two delta fields;
 //   pad          (uint32)   0
 // and / or to the copy itself, base[i] = w[i] bit for bit (NaN payloads included), which starts the next window.  Driven by a chunk
-// table (multitensor.h); like the statistics (stats.hip) a kernel of its own that runs BETWEEN two training iterations and only
-// READS what the step left.  The reference has nothing of the kind.
+// table (multitensor.h); a kernel of its own that runs BETWEEN two training iterations and only READS what the step left.  The
+// reference has nothing of the kind.
 //
 // MODE (a template parameter): DYN_RECORD (1) writes the records and only reads base; DYN_REBASE (2) copies and writes no record;
 // 3 does both in one pass - every thread stores after its own loads of the same elements, so the record describes the old base.
 //
-// Structure, load paths and grid cap are those of stats.hip.  (1) locate_dyn_partial_kernel: one block per 4096-element chunk, at
+// Two launches on the chunk-table layer of multitensor.h.  (1) locate_dyn_partial_kernel: one block per 4096-element chunk, at
 // most mt_grid blocks striding over the chunk table, writes that chunk's partial record to workspace[position of the chunk in the
-// chunk table]; 16-byte loads (and stores) where BOTH w + begin and base + begin are 16-byte aligned, 4-byte ones otherwise.
-// (2) locate_dyn_combine_kernel: one block per tensor adds the partials of its chunks in a fixed order and writes the record.
-// DYN_REBASE alone is the first launch only and touches neither records nor workspace.
+// chunk table]; w and base are read together in fixed lanes (mt_read_lanes: 16-byte loads where BOTH are 16-byte aligned at the
+// chunk, 4-byte ones otherwise) and the copy is written the same way (mt_write_lanes).  (2) locate_dyn_combine_kernel: one block
+// per tensor adds the partials of its chunks in a fixed order and writes the record.  DYN_REBASE alone is the first launch only
+// and touches neither records nor workspace.
 //
 // A record depends only on its tensor's contents and length - not on the grid, on the tensor's position in the table, on what else
-// the table holds, nor on the alignment of w or base: element 4 (t + 256 k) + j of a chunk always belongs to thread t (k, j < 4),
-// whether it arrived by a 16-byte or a 4-byte load, and every sum has one order - a thread's elements in index order, a wave by a
-// butterfly, the block's four waves in order, partial p on thread p % 256 in ascending order.  No floating-point atomics, no
-// atomics at all.  Missing elements of a short chunk enter as w = base = +0.0: they change neither sum nor the maximum nor the
-// non-finite count, and thread 0 takes their number off the chunk's `unchanged`.
+// the table holds, nor on the alignment of w or base: an element belongs to the same thread however it was loaded, and every sum
+// has the one order of multitensor.h's mt_block_total and mt_add_partials.  No floating-point atomics, no atomics at all.
+// Missing elements of a short chunk enter as w = base = +0.0: they change neither sum nor the maximum nor the non-finite count,
+// and thread 0 takes their number off the chunk's `unchanged`.
 //
 // A bandwidth kernel (8 bytes read per element in mode 1, 4 read and 4 written in mode 2): a full chunk's eight 16-byte loads in
 // flight per thread before the first use.  Ordinary stores (profiles/notes_snapshot.md could not tell them from nontemporal ones).
@@ -49,6 +49,13 @@ struct DynRecord {          // a chunk's partial and a tensor's record alike
     unsigned unchanged;
     unsigned nonfinite;
     unsigned pad;
+    __device__ __forceinline__ void add(const DynRecord& q) {
+        delta_sumsq += q.delta_sumsq;
+        base_sumsq += q.base_sumsq;
+        delta_absmax = q.delta_absmax > delta_absmax ? q.delta_absmax : delta_absmax;
+        unchanged += q.unchanged;
+        nonfinite += q.nonfinite;
+    }
 };
 
 __device__ __forceinline__ void dyn_take(float w, float b, DynRecord& r) {
@@ -70,38 +77,6 @@ __device__ __forceinline__ void dyn_take4(float4 w, float4 b, DynRecord& r) {
     dyn_take(w.w, b.w, r);
 }
 
-__device__ __forceinline__ void dyn_add(DynRecord& r, const DynRecord& q) {
-    r.delta_sumsq += q.delta_sumsq;
-    r.base_sumsq += q.base_sumsq;
-    r.delta_absmax = q.delta_absmax > r.delta_absmax ? q.delta_absmax : r.delta_absmax;
-    r.unchanged += q.unchanged;
-    r.nonfinite += q.nonfinite;
-}
-
-// the block's total in thread 0 (other threads: unspecified); `lds` holds MT_WAVES records
-__device__ __forceinline__ DynRecord dyn_block_reduce(DynRecord r, DynRecord* lds) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        DynRecord q;
-        q.delta_sumsq = __shfl_xor(r.delta_sumsq, o, 64);
-        q.base_sumsq = __shfl_xor(r.base_sumsq, o, 64);
-        q.delta_absmax = (unsigned)__shfl_xor((int)r.delta_absmax, o, 64);
-        q.unchanged = (unsigned)__shfl_xor((int)r.unchanged, o, 64);
-        q.nonfinite = (unsigned)__shfl_xor((int)r.nonfinite, o, 64);
-        dyn_add(r, q);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();          // lds may still be read from the previous chunk
-    if (lane == 0) lds[wid] = r;
-    __syncthreads();
-    DynRecord total = lds[0];
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int w = 1; w < MT_WAVES; ++w) dyn_add(total, lds[w]);
-    }
-    return total;
-}
-
 template <int MODE>
 __global__ void __launch_bounds__(MT_THREADS) locate_dyn_partial_kernel(const DynTensor* __restrict__ tensors, const int2* __restrict__ chunks,
                                                                           int n_tensors, int n_chunks, DynRecord* __restrict__ partials) {
@@ -114,78 +89,16 @@ __global__ void __launch_bounds__(MT_THREADS) locate_dyn_partial_kernel(const Dy
         int len;
         // a damaged table writes nothing
         if (!mt_decode(tensors, n_tensors, ch, T, begin, len) || (long long)T.first_chunk + ch.y != c || !T.w || !T.base) continue;
-        const float* w = T.w + begin;
-        float* b = T.base + begin;
-        const bool vec = ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
-        float4 wv[MT_PER_THREAD], bv[MT_PER_THREAD];
-        if (vec && len == MT_CHUNK) {          // a full chunk: every load issued before the first use
-            const float4* w4 = reinterpret_cast<const float4*>(w);
-            float4* b4 = reinterpret_cast<float4*>(b);
-#pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) wv[k] = w4[threadIdx.x + k * MT_THREADS];
-            if (REC) {
-#pragma unroll
-                for (int k = 0; k < MT_PER_THREAD; ++k) bv[k] = b4[threadIdx.x + k * MT_THREADS];
-            }
-            if (COPY) {
-#pragma unroll
-                for (int k = 0; k < MT_PER_THREAD; ++k) b4[threadIdx.x + k * MT_THREADS] = wv[k];
-            }
-        } else if (vec) {
-            const float4* w4 = reinterpret_cast<const float4*>(w);
-            float4* b4 = reinterpret_cast<float4*>(b);
-#pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) {
-                const int e = 4 * (threadIdx.x + k * MT_THREADS);
-                if (e + 4 <= len) {
-                    wv[k] = w4[threadIdx.x + k * MT_THREADS];
-                    if (REC) bv[k] = b4[threadIdx.x + k * MT_THREADS];
-                    if (COPY) b4[threadIdx.x + k * MT_THREADS] = wv[k];
-                } else {
-                    wv[k].x = e < len ? w[e] : 0.0f;
-                    wv[k].y = e + 1 < len ? w[e + 1] : 0.0f;
-                    wv[k].z = e + 2 < len ? w[e + 2] : 0.0f;
-                    wv[k].w = 0.0f;          // e + 3 < len would have taken the 16-byte path
-                    if (REC) {
-                        bv[k].x = e < len ? b[e] : 0.0f;
-                        bv[k].y = e + 1 < len ? b[e + 1] : 0.0f;
-                        bv[k].z = e + 2 < len ? b[e + 2] : 0.0f;
-                        bv[k].w = 0.0f;
-                    }
-                    if (COPY) {
-                        if (e < len) b[e] = wv[k].x;
-                        if (e + 1 < len) b[e + 1] = wv[k].y;
-                        if (e + 2 < len) b[e + 2] = wv[k].z;
-                    }
-                }
-            }
-        } else {          // w or base not 16-byte aligned: the same elements per thread through 4-byte loads and stores
-#pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) {
-                const int e = 4 * (threadIdx.x + k * MT_THREADS);
-                wv[k].x = e < len ? w[e] : 0.0f;
-                wv[k].y = e + 1 < len ? w[e + 1] : 0.0f;
-                wv[k].z = e + 2 < len ? w[e + 2] : 0.0f;
-                wv[k].w = e + 3 < len ? w[e + 3] : 0.0f;
-                if (REC) {
-                    bv[k].x = e < len ? b[e] : 0.0f;
-                    bv[k].y = e + 1 < len ? b[e + 1] : 0.0f;
-                    bv[k].z = e + 2 < len ? b[e + 2] : 0.0f;
-                    bv[k].w = e + 3 < len ? b[e + 3] : 0.0f;
-                }
-                if (COPY) {
-                    if (e < len) b[e] = wv[k].x;
-                    if (e + 1 < len) b[e + 1] = wv[k].y;
-                    if (e + 2 < len) b[e + 2] = wv[k].z;
-                    if (e + 3 < len) b[e + 3] = wv[k].w;
-                }
-            }
-        }
+        float4 v[2][MT_PER_THREAD];          // w, and base when recording
+        const float* const src[2] = {T.w + begin, T.base + begin};
+        if (REC) mt_read_lanes(src, len, v);          // the loads ahead of the store: the record describes the old base
+        else mt_read_lanes(src[0], len, v[0]);
+        if (COPY) mt_write_lanes(T.base + begin, len, v[0]);
         if (REC) {
             DynRecord r = {0.0, 0.0, 0u, 0u, 0u, 0u};
 #pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) dyn_take4(wv[k], bv[k], r);
-            r = dyn_block_reduce(r, lds);
+            for (int k = 0; k < MT_PER_THREAD; ++k) dyn_take4(v[0][k], v[1][k], r);
+            r = mt_block_total(r, lds);
             if (threadIdx.x == 0) {
                 r.unchanged -= (unsigned)(MT_CHUNK - len);          // the +0.0 == +0.0 of a short chunk's missing elements
                 r.pad = 0u;
@@ -203,10 +116,9 @@ __global__ void __launch_bounds__(MT_THREADS) locate_dyn_combine_kernel(const Dy
         if (T.n <= 0 || T.first_chunk < 0 || !T.w || !T.base) continue;          // a damaged table writes nothing
         const long long nc = (T.n + MT_CHUNK - 1) / MT_CHUNK;
         if ((long long)T.first_chunk + nc > n_chunks) continue;
-        const DynRecord* p = partials + T.first_chunk;
         DynRecord r = {0.0, 0.0, 0u, 0u, 0u, 0u};
-        for (int i = threadIdx.x; i < (int)nc; i += MT_THREADS) dyn_add(r, p[i]);          // partial p on thread p % 256, ascending
-        r = dyn_block_reduce(r, lds);
+        mt_add_partials(partials + T.first_chunk, (int)nc, r);
+        r = mt_block_total(r, lds);
         if (threadIdx.x == 0) {
             r.pad = 0u;
             records[t] = r;

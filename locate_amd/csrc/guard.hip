@@ -10,11 +10,12 @@
 //                              partials[chunk position];
 //   (2) guard_verdict_kernel   one block adds the partials in a fixed order and writes the verdict record (GuardVerdict below);
 //   (3) guarded_schedule_kernel / guarded_update_kernel, once per parameter group: nadam.hip's pair, reading the verdict.
-// No floating-point atomics: every sum has a fixed order (multitensor.h's reduction, shared with stats.hip), so two steps over the
-// same gradients at the same addresses reach the same verdict bit for bit.  Unlike stats.hip's records the sum DOES depend on a
-// tensor's alignment: a tensor that is only 4-byte aligned (the data-parallel bucket views) is read with 16-byte loads between a
-// scalar head and tail, so the 16-byte words fall on other elements than in an aligned tensor and the additions associate
-// differently (within n 2^-52 relative either way).
+// No floating-point atomics: every sum has a fixed order (multitensor.h's mt_block_total and mt_add_partials), so two steps over
+// the same gradients at the same addresses reach the same verdict bit for bit.  Unlike the statistics' records the sum DOES depend
+// on a tensor's alignment: a chunk is read split at the 16-byte boundaries (multitensor.h's mt_read_split: a tensor that is only
+// 4-byte aligned, as the data-parallel bucket views are, is read with 16-byte loads between a per-word head and tail), so the
+// 16-byte words fall on other elements than in an aligned tensor and the additions associate differently (within n 2^-52
+// relative either way).
 //
 // The update: g' = g * scale is ONE separately rounded fp32 multiply (never fused into the operations behind it), then Nadam's
 // arithmetic runs on g': both steps instantiate the one spelled-out element of nadam_step.h.  Weight decay is added after the scaling,
@@ -41,70 +42,65 @@ struct GuardVerdict {               // 64 bytes, 8-byte aligned; the counters ru
     double sumsq;                   // the total norm is the root of
 };
 
+// MtPartial's layout with an add() that leaves the maximum out: the verdict never reads it, carrying it cost the step 2.2 us
+// (multitensor.h, mt_take), and the partials' absmax stays 0
+struct GuardPartial {
+    double sumsq;
+    unsigned absmax;
+    unsigned nonfinite;
+    __device__ __forceinline__ void add(const GuardPartial& q) {
+        sumsq += q.sumsq;
+        nonfinite += q.nonfinite;
+    }
+};
+static_assert(sizeof(GuardPartial) == sizeof(MtPartial), "the guard's workspace holds MtPartial-sized records");
+
+struct GuardTotal {          // the count is kept in 64 bits from the verdict on (a chunk's fits 32)
+    double sumsq;
+    unsigned long long nonfinite;
+    __device__ __forceinline__ void add(const GuardPartial& q) {
+        sumsq += q.sumsq;
+        nonfinite += q.nonfinite;
+    }
+    __device__ __forceinline__ void add(const GuardTotal& q) {
+        sumsq += q.sumsq;
+        nonfinite += q.nonfinite;
+    }
+};
+
 __global__ void __launch_bounds__(MT_THREADS) guard_reduce_kernel(const GuardTensor* __restrict__ tensors, const int2* __restrict__ chunks,
-                                                                 int n_tensors, int n_chunks, MtPartial* __restrict__ partials) {
-    __shared__ MtPartial lds[MT_WAVES];
+                                                                 int n_tensors, int n_chunks, GuardPartial* __restrict__ partials) {
+    __shared__ GuardPartial lds[MT_WAVES];
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-        double s = 0.0;
-        unsigned amax = 0u, cnt = 0u;          // the shared reduction without its maximum: the partials' absmax stays 0
+        GuardPartial r = {0.0, 0u, 0u};
         GuardTensor T;
         long long begin;
         int len;
         // a damaged table entry contributes nothing (and reads nothing); its partial is still written: the verdict adds them all
         if (mt_decode(tensors, n_tensors, chunks[c], T, begin, len)) {
             const float* x = T.g + begin;
-            // elements up to the first 16-byte boundary (0 .. 3 of them), 16-byte words, the rest (0 .. 3)
-            int head = (int)((16 - (reinterpret_cast<uintptr_t>(x) & 15)) & 15) >> 2;
-            if (head > len) head = len;
-            const int n4 = (len - head) >> 2;
-            const int tail = len - head - 4 * n4;
-            const float4* x4 = reinterpret_cast<const float4*>(x + head);
-            const float* xt = x + head + 4 * n4;
-            float4 v[MT_PER_THREAD];
+            mt_word4<float> v[MT_PER_THREAD];
+            float h, t;
+            mt_read_split(x, mt_split(x, len), v, h, t);          // +0.0 where the chunk has no word: it changes neither result
+            mt_take<false>(h, r.sumsq, r.absmax, r.nonfinite);
 #pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) {          // every load issued before the first use
-                const int w = threadIdx.x + k * MT_THREADS;
-                v[k] = w < n4 ? x4[w] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);          // +0.0 changes neither result
-            }
-            const float h = (int)threadIdx.x < head ? x[threadIdx.x] : 0.0f;
-            const float t = (int)threadIdx.x < tail ? xt[threadIdx.x] : 0.0f;
-            mt_take<false>(h, s, amax, cnt);
-#pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) mt_take4<false>(v[k], s, amax, cnt);
-            mt_take<false>(t, s, amax, cnt);
+            for (int k = 0; k < MT_PER_THREAD; ++k) mt_take4<false>(v[k], r.sumsq, r.absmax, r.nonfinite);
+            mt_take<false>(t, r.sumsq, r.absmax, r.nonfinite);
         }
-        const MtPartial r = mt_block_reduce<false>(s, amax, cnt, lds);
+        r = mt_block_total(r, lds);
         if (threadIdx.x == 0) partials[c] = r;          // c < n_chunks: inside the workspace
     }
 }
 
-// the count is kept in 64 bits from here on (a chunk's fits 32), so the block's last stage is this kernel's own
-__global__ void __launch_bounds__(MT_THREADS) guard_verdict_kernel(const MtPartial* __restrict__ partials, int n_chunks,
+__global__ void __launch_bounds__(MT_THREADS) guard_verdict_kernel(const GuardPartial* __restrict__ partials, int n_chunks,
                                                                   GuardVerdict* __restrict__ verdict, double max_norm, int skip_nonfinite) {
-    __shared__ double lds_s[MT_WAVES];
-    __shared__ unsigned long long lds_c[MT_WAVES];
-    double s = 0.0;
-    unsigned amax = 0u;
-    unsigned long long cnt = 0ull;
-    mt_add_partials(partials, n_chunks, s, amax, cnt);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o, 64);
-        cnt += (unsigned long long)__shfl_xor((long long)cnt, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        lds_s[threadIdx.x >> 6] = s;
-        lds_c[threadIdx.x >> 6] = cnt;
-    }
-    __syncthreads();
+    __shared__ GuardTotal lds[MT_WAVES];
+    GuardTotal total = {0.0, 0ull};
+    mt_add_partials(partials, n_chunks, total);
+    total = mt_block_total(total, lds);
     if (threadIdx.x != 0) return;
-    s = lds_s[0];
-    cnt = lds_c[0];
-#pragma unroll
-    for (int w = 1; w < MT_WAVES; ++w) {
-        s += lds_s[w];
-        cnt += lds_c[w];
-    }
+    const double s = total.sumsq;
+    const unsigned long long cnt = total.nonfinite;
     GuardVerdict V = *verdict;
     const double norm = sqrt(s);
     const int skip = skip_nonfinite && cnt > 0ull ? 1 : 0;
@@ -138,7 +134,7 @@ LOCATE_API size_t locate_guard_tensor_record_bytes(void) { return sizeof(GuardTe
 LOCATE_API size_t locate_guard_verdict_bytes(void) { return sizeof(GuardVerdict); }
 LOCATE_API int locate_guard_chunk_elems(void) { return MT_CHUNK; }
 LOCATE_API int locate_guard_max_blocks(void) { return mt_grid(0x7fffffff); }
-LOCATE_API size_t locate_guard_workspace_bytes(int n_chunks) { return n_chunks > 0 ? (size_t)n_chunks * sizeof(MtPartial) : 0; }
+LOCATE_API size_t locate_guard_workspace_bytes(int n_chunks) { return n_chunks > 0 ? (size_t)n_chunks * sizeof(GuardPartial) : 0; }
 
 // One optimizer step behind a verdict.
 //   grads / grad_chunks: DEVICE array of n_grads {const float* g; int64 n} records over EVERY gradient of the optimizer, and the
@@ -164,9 +160,9 @@ LOCATE_API int locate_guarded_nadam_step(const void* grads, const void* grad_chu
     GuardVerdict* V = static_cast<GuardVerdict*>(verdict);
     if (n_grads > 0) {
         guard_reduce_kernel<<<mt_grid(n_grad_chunks), MT_THREADS, 0, st>>>(static_cast<const GuardTensor*>(grads), static_cast<const int2*>(grad_chunks),
-                                                                           n_grads, n_grad_chunks, static_cast<MtPartial*>(workspace));
+                                                                           n_grads, n_grad_chunks, static_cast<GuardPartial*>(workspace));
         LOCATE_LAUNCH_CHECK("locate_guarded_nadam_step(reduce)");
-        guard_verdict_kernel<<<1, MT_THREADS, 0, st>>>(static_cast<const MtPartial*>(workspace), n_grad_chunks, V, max_norm, skip_nonfinite);
+        guard_verdict_kernel<<<1, MT_THREADS, 0, st>>>(static_cast<const GuardPartial*>(workspace), n_grad_chunks, V, max_norm, skip_nonfinite);
         LOCATE_LAUNCH_CHECK("locate_guarded_nadam_step(verdict)");
     }
     guarded_schedule_kernel<<<(n_tensors + 63) / 64, 64, 0, st>>>(static_cast<const NadamTensor*>(tensors), static_cast<NadamCoef*>(coef),

@@ -17,8 +17,9 @@
 //
 // A pure bandwidth kernel (8 bytes per word): 16-byte loads and stores where the live pointer is 16-byte aligned at the chunk
 // (slot offsets are multiples of 16, so only the live side varies), otherwise 16-byte accesses on the live side between a
-// per-word head and tail and per-word accesses on the slot side, as guard.hip reads the 4-byte-aligned bucket views.  Every load
-// of a chunk is issued before its first store; at most 2048 blocks (256 CUs x 8) stride over the chunk table.
+// per-word head and tail and per-word accesses on the slot side: the split is multitensor.h's (mt_split), the loads and the
+// stores are this file's.  Every load of a chunk is issued before its first store; at most 2048 blocks (256 CUs x 8) stride over
+// the chunk table.  A block's count is multitensor.h's mt_block_total.
 //
 // SNAPSHOT_NONTEMPORAL: the destination slot is not read again for hundreds of iterations, and a take pushes a slot's worth of
 // stores through the Infinity Cache the next iteration's weights sit in.  Both store forms are compiled.  Measured, the take PLUS
@@ -93,16 +94,15 @@ __device__ __forceinline__ u32x4 snap_load4(const unsigned* p, bool vec) {
     return v;
 }
 
-// Words [0, len) of a chunk from src to dst, 0 < len <= MT_CHUNK: `head` words (0 .. 3, up to the LIVE side's first 16-byte
-// boundary), 16-byte words, the rest (0 .. 3).  src_vec / dst_vec: whether that side is 16-byte aligned at src + head / dst + head
-// (the live side always is, the slot side only when head == 0).  Every load before the first store.  Returns this thread's
-// count of words that are non-finite for `kind`; the chunk starts at an even word of its tensor.
+// Words [0, len) of a chunk from src to dst in multitensor.h's split `s` of the LIVE side: head words, 16-byte words, the rest.
+// src_vec / dst_vec: whether that side is 16-byte aligned at src + head / dst + head (the live side always is, the slot side only
+// when head == 0).  Every load before the first store.  Returns this thread's count of words that are non-finite for `kind`; the
+// chunk starts at an even word of its tensor.  The loads are this file's own, not mt_read_split: with the shared read the copy
+// kernel went from 90 to 58 VGPRs and the restore ran 46 us longer (profiles/notes_multitensor.md).
 template <bool NT, bool JUDGE>
-__device__ __forceinline__ unsigned snap_copy_chunk(const unsigned* __restrict__ src, unsigned* __restrict__ dst, int len, int head,
+__device__ __forceinline__ unsigned snap_copy_chunk(const unsigned* __restrict__ src, unsigned* __restrict__ dst, const MtSplit& s,
                                                     bool src_vec, bool dst_vec, int kind) {
-    const int n4 = (len - head) >> 2;
-    const int tail = len - head - 4 * n4;
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, head = s.head, n4 = s.n4, tail = s.tail;
     u32x4 v[MT_PER_THREAD];
 #pragma unroll
     for (int k = 0; k < MT_PER_THREAD; ++k) {
@@ -134,21 +134,24 @@ __device__ __forceinline__ unsigned snap_copy_chunk(const unsigned* __restrict__
     return bad;
 }
 
-// words up to the first 16-byte boundary of p, at most len
-__device__ __forceinline__ int snap_head(const unsigned* p, int len) {
-    const int head = (int)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2;
-    return head > len ? len : head;
-}
+// what a take found: words that are non-finite for their kind, and the lowest tensor index that has one.  32 bits hold a block's
+// count: a thread sees at most 18 words per chunk and a block at most 1 / 2048 of a table that fits the device's memory.
+struct SnapBad {
+    unsigned count;
+    int first;
+    __device__ __forceinline__ void add(const SnapBad& q) {
+        count += q.count;
+        first = q.first < first ? q.first : first;
+    }
+};
 
 template <bool NT>
 __global__ void __launch_bounds__(MT_THREADS) snapshot_copy_kernel(const SnapshotTensor* __restrict__ tensors, const int2* __restrict__ chunks,
                                                                   int n_tensors, int n_chunks, unsigned* slot0, unsigned* slot1,
                                                                   SnapshotCommit* commit) {
-    __shared__ unsigned lds_c[MT_WAVES];
-    __shared__ int lds_t[MT_WAVES];
+    __shared__ SnapBad lds[MT_WAVES];
     unsigned* slot = commit->good == 0 ? slot1 : slot0;          // the slot that is NOT the good one; uniform
-    unsigned cnt = 0u;          // a thread sees at most 18 words per chunk: 32 bits hold any table
-    int first = INT_MAX;
+    SnapBad found = {0u, INT_MAX};
     for (int c = blockIdx.x; c < n_chunks; c += gridDim.x) {
         SnapshotTensor T;
         long long begin;
@@ -169,33 +172,15 @@ __global__ void __launch_bounds__(MT_THREADS) snapshot_copy_kernel(const Snapsho
             continue;
         }
         const unsigned* src = T.live + begin;
-        const int head = snap_head(src, len);
-        const unsigned bad = snap_copy_chunk<NT, true>(src, dst, len, head, true, head == 0, T.kind);
-        cnt += bad;
-        first = bad != 0u && ch.x < first ? ch.x : first;
+        const MtSplit s = mt_split(src, len);
+        const unsigned bad = snap_copy_chunk<NT, true>(src, dst, s, true, s.head == 0, T.kind);
+        found.count += bad;
+        found.first = bad != 0u && ch.x < found.first ? ch.x : found.first;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        cnt += (unsigned)__shfl_xor((int)cnt, o, 64);
-        const int of = __shfl_xor(first, o, 64);
-        first = of < first ? of : first;
-    }
-    if ((threadIdx.x & 63) == 0) {
-        lds_c[threadIdx.x >> 6] = cnt;
-        lds_t[threadIdx.x >> 6] = first;
-    }
-    __syncthreads();
-    if (threadIdx.x != 0) return;
-    unsigned long long total = lds_c[0];
-    first = lds_t[0];
-#pragma unroll
-    for (int w = 1; w < MT_WAVES; ++w) {
-        total += lds_c[w];
-        first = lds_t[w] < first ? lds_t[w] : first;
-    }
-    if (total != 0ull) {
-        atomicAdd(&commit->bad_words, total);
-        atomicMin(&commit->bad_tensor, first);
+    found = mt_block_total(found, lds);
+    if (threadIdx.x == 0 && found.count != 0u) {
+        atomicAdd(&commit->bad_words, (unsigned long long)found.count);
+        atomicMin(&commit->bad_tensor, found.first);
     }
 }
 
@@ -225,8 +210,8 @@ __global__ void __launch_bounds__(MT_THREADS) snapshot_restore_kernel(const Snap
         int len;
         if (!mt_decode(tensors, n_tensors, chunks[c], T, begin, len) || T.live == nullptr) continue;
         unsigned* dst = T.live + begin;
-        const int head = snap_head(dst, len);
-        (void)snap_copy_chunk<false, false>(slot + (T.offset >> 2) + begin, dst, len, head, head == 0, true, 0);
+        const MtSplit s = mt_split(dst, len);
+        (void)snap_copy_chunk<false, false>(slot + (T.offset >> 2) + begin, dst, s, s.head == 0, true, 0);
     }
 }
 

@@ -16,9 +16,9 @@
 // boundary (~2 us) behind a kernel that runs for tens of microseconds.
 //
 // A record depends only on its tensor's contents and length - not on the grid, on the tensor's position in the table, on what else
-// the table holds, nor on the tensor's alignment: element 4 (t + 256 k) + j of a chunk always belongs to thread t (k, j < 4),
-// whether it arrived by a 16-byte or a 4-byte load, and every sum has the one order of multitensor.h's reduction.  Missing elements
-// of a short chunk enter as +0.0, which changes none of the three results.
+// the table holds, nor on the tensor's alignment: a chunk is read in multitensor.h's fixed lanes (mt_read_lanes: an element belongs
+// to the same thread whether it arrived by a 16-byte or a 4-byte load) and every sum has the one order of multitensor.h's
+// mt_block_total and mt_add_partials.  Missing elements of a short chunk enter as +0.0, which changes none of the three results.
 // No floating-point atomics; the summary is built with integer atomics (an add and a minimum: order-free, so deterministic).
 //
 // A pure bandwidth kernel (4 bytes per element, ~3 operations): 16-byte loads where the chunk is 16-byte aligned, a full chunk's
@@ -49,41 +49,12 @@ __global__ void __launch_bounds__(MT_THREADS) locate_stats_partial_kernel(const 
         int len;
         // a damaged table writes nothing
         if (!mt_decode(tensors, n_tensors, ch, T, begin, len) || (long long)T.first_chunk + ch.y != c) continue;
-        const float* x = T.x + begin;
         float4 v[MT_PER_THREAD];
-        if ((reinterpret_cast<uintptr_t>(x) & 15) == 0 && len == MT_CHUNK) {          // a full chunk: every load issued before the first use
-            const float4* x4 = reinterpret_cast<const float4*>(x);
+        mt_read_lanes(T.x + begin, len, v);
+        StatsRecord r = {0.0, 0u, 0u};
 #pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) v[k] = x4[threadIdx.x + k * MT_THREADS];
-        } else if ((reinterpret_cast<uintptr_t>(x) & 15) == 0) {
-            const float4* x4 = reinterpret_cast<const float4*>(x);
-#pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) {
-                const int e = 4 * (threadIdx.x + k * MT_THREADS);
-                if (e + 4 <= len) {
-                    v[k] = x4[threadIdx.x + k * MT_THREADS];
-                } else {
-                    v[k].x = e < len ? x[e] : 0.0f;
-                    v[k].y = e + 1 < len ? x[e + 1] : 0.0f;
-                    v[k].z = e + 2 < len ? x[e + 2] : 0.0f;
-                    v[k].w = 0.0f;          // e + 3 < len would have taken the 16-byte load
-                }
-            }
-        } else {          // a base that is not 16-byte aligned: the same elements per thread through 4-byte loads
-#pragma unroll
-            for (int k = 0; k < MT_PER_THREAD; ++k) {
-                const int e = 4 * (threadIdx.x + k * MT_THREADS);
-                v[k].x = e < len ? x[e] : 0.0f;
-                v[k].y = e + 1 < len ? x[e + 1] : 0.0f;
-                v[k].z = e + 2 < len ? x[e + 2] : 0.0f;
-                v[k].w = e + 3 < len ? x[e + 3] : 0.0f;
-            }
-        }
-        double s = 0.0;
-        unsigned m = 0u, cnt = 0u;
-#pragma unroll
-        for (int k = 0; k < MT_PER_THREAD; ++k) mt_take4(v[k], s, m, cnt);
-        const StatsRecord r = mt_block_reduce(s, m, cnt, lds);
+        for (int k = 0; k < MT_PER_THREAD; ++k) mt_take4(v[k], r.sumsq, r.absmax, r.nonfinite);
+        r = mt_block_total(r, lds);
         if (threadIdx.x == 0) partials[c] = r;          // c < n_chunks: inside the workspace
     }
 }
@@ -97,11 +68,9 @@ __global__ void __launch_bounds__(MT_THREADS) locate_stats_combine_kernel(const 
         if (T.n <= 0 || T.first_chunk < 0) continue;          // a damaged table writes nothing
         const long long nc = (T.n + MT_CHUNK - 1) / MT_CHUNK;
         if ((long long)T.first_chunk + nc > n_chunks) continue;
-        const StatsRecord* p = partials + T.first_chunk;
-        double s = 0.0;
-        unsigned m = 0u, cnt = 0u;
-        mt_add_partials(p, (int)nc, s, m, cnt);
-        const StatsRecord r = mt_block_reduce(s, m, cnt, lds);
+        StatsRecord r = {0.0, 0u, 0u};
+        mt_add_partials(partials + T.first_chunk, (int)nc, r);
+        r = mt_block_total(r, lds);
         if (threadIdx.x == 0) {
             records[t] = r;
             if (r.nonfinite) {          // integer atomics: the result does not depend on the order of arrival

@@ -29,8 +29,7 @@ import struct
 import numpy as np
 import torch
 
-from ._tables import chunk_pairs, stage
-from .stats import _require_device_tensors
+from ._tables import arena_layout, chunk_pairs, require_device_tensors, stage
 
 RECORD, REBASE = 1, 2          # the modes of locate_dyn_pass; 3 is both in one pass
 WORDS = 4          # int64 words of a 32-byte record
@@ -75,7 +74,7 @@ def tensor_deltas(tensors, bases):
     tensors, bases = list(tensors), list(bases)
     if not tensors or len(tensors) != len(bases):
         raise ValueError("tensor_deltas needs as many bases as tensors, and at least one: got %d and %d" % (len(tensors), len(bases)))
-    _require_device_tensors(tensors + bases, "tensor_deltas")
+    require_device_tensors(tensors + bases, "tensor_deltas")
     for t, b in zip(tensors, bases):
         if t.numel() != b.numel():
             raise ValueError("tensor_deltas: a tensor of %d elements against a base of %d" % (t.numel(), b.numel()))
@@ -95,10 +94,6 @@ def tensor_deltas(tensors, bases):
 
 def _is_uv(name):
     return name.endswith(("weight_u", "weight_v"))
-
-
-def _round4(n):
-    return -(-n // 4) * 4
 
 
 class RunDynamics:
@@ -201,17 +196,14 @@ class RunDynamics:
         if key == self._key:
             return
         tensors = [p.detach() for _, p in params]
-        _require_device_tensors(tensors, "RunDynamics")
+        require_device_tensors(tensors, "RunDynamics")
         dev = tensors[0].device
         layers = self._sn_layers()
         if self._arena is None:
-            offsets, total = [], 0
-            for t in tensors:
-                offsets.append(total)
-                total += _round4(t.numel())          # every slot starts on a 16-byte boundary
-            self._arena = torch.zeros(total, dtype=torch.float32, device=dev)
+            offsets, nbytes = arena_layout([t.numel() for t in tensors])          # every slot starts on a 16-byte boundary
+            self._arena = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
             assert self._arena.data_ptr() % 16 == 0
-            self._slots = [self._arena[o:o + t.numel()] for o, t in zip(offsets, tensors)]
+            self._slots = [self._arena[o // 4:o // 4 + t.numel()] for o, t in zip(offsets, tensors)]
             self._ring = torch.zeros(self.capacity, WORDS * len(tensors) + len(layers), dtype=torch.int64, device=dev)
             self._names, self._layer_names = tuple(n for n, _ in params), tuple(n for n, _ in layers)
         self._tab = _device_table(tensors, self._slots)
@@ -233,17 +225,15 @@ class RunDynamics:
             h = w.shape[0]
             geometry.append((h, w.numel() // h, (h + 63) // 64))
         if self._sn is None or "shadow" not in self._sn:
-            at, total = {}, 0
+            sizes = {}
             for s in range(2):          # train, top
                 for i, (h, wd, nch) in enumerate(geometry):
-                    for what, size in (("u", h), ("v", wd), ("wv", h)):
-                        at[s, i, what] = total
-                        total += _round4(size)
+                    sizes.update({(s, i, "u"): h, (s, i, "v"): wd, (s, i, "wv"): h})
             for i, (h, wd, nch) in enumerate(geometry):
-                for what, size in (("t", wd), ("s", h), ("tpart", nch * wd)):
-                    at[i, what] = total
-                    total += _round4(size)
-            self._sn = {"shadow": torch.zeros(total, dtype=torch.float32, device=dev), "at": at,
+                sizes.update({(i, "t"): wd, (i, "s"): h, (i, "tpart"): nch * wd})
+            offsets, nbytes = arena_layout(sizes.values())
+            at = {key: o // 4 for key, o in zip(sizes, offsets)}
+            self._sn = {"shadow": torch.zeros(nbytes // 4, dtype=torch.float32, device=dev), "at": at,
                         "sigma": torch.zeros(2, n, 2, dtype=torch.float32, device=dev)}          # [set, layer, {sigma, 1 / sigma}]
         sn_state = self._sn
         shadow, at, sigma = sn_state["shadow"], sn_state["at"], sn_state["sigma"]

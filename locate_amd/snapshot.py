@@ -30,7 +30,7 @@ import struct
 
 import torch
 
-from ._tables import chunk_pairs, remember, stage
+from ._tables import arena_layout, chunk_pairs, remember, stage  # noqa: F401  (arena_layout is part of this module's interface)
 
 RECORD_BYTES = 48
 COMMIT_BYTES = 64
@@ -43,19 +43,6 @@ SCHED_FILL = struct.unpack("<4I", struct.pack("<2d", 0.0, 1.0))          # Nadam
 
 class NoSnapshot(RuntimeError):
     """restore() without a committed slot: no take has passed its check yet (or the run was just resumed)."""
-
-
-def arena_layout(word_counts):
-    """(byte offset of every tensor in a slot, slot_bytes) for tensors of `word_counts` 4-byte words: in order, every offset a
-    multiple of 16, a zero-length tensor takes no space."""
-    offsets, at = [], 0
-    for n in word_counts:
-        n = int(n)
-        if n < 0:
-            raise ValueError("a tensor of %d words" % n)
-        offsets.append(at)
-        at += (4 * n + 15) // 16 * 16
-    return offsets, at
 
 
 def _fill_words(fill):

@@ -26,7 +26,7 @@ import struct
 import numpy as np
 import torch
 
-from ._tables import chunk_pairs, stage
+from ._tables import chunk_pairs, require_device_tensors, stage
 
 
 class NonFiniteError(RuntimeError):
@@ -41,14 +41,6 @@ class NonFiniteError(RuntimeError):
             shown += ", ... %d more" % (len(self.tensors) - 4)
         super().__init__("non-finite values at iteration %d in %d tensor%s: %s"
                          % (self.iteration, len(self.tensors), "" if len(self.tensors) == 1 else "s", shown))
-
-
-def _require_device_tensors(tensors, what):
-    for t in tensors:
-        if not torch.is_tensor(t) or not t.is_cuda:
-            raise TypeError("%s computes on the GPU only; got %s" % (what, t.device if torch.is_tensor(t) else type(t).__name__))
-        if t.dtype != torch.float32 or not t.is_contiguous():
-            raise TypeError("%s takes contiguous float32 tensors, got %s%s" % (what, t.dtype, "" if t.is_contiguous() else " (strided)"))
 
 
 def _device_table(tensors):
@@ -79,7 +71,7 @@ def tensor_statistics(tensors):
     tensors = list(tensors)
     if not tensors:
         raise ValueError("tensor_statistics needs at least one tensor")
-    _require_device_tensors(tensors, "tensor_statistics")
+    require_device_tensors(tensors, "tensor_statistics")
     dev = tensors[0].device
     live = [i for i, t in enumerate(tensors) if t.numel() > 0]
     k = len(tensors)
@@ -207,7 +199,7 @@ class RunStatistics:
         if key != self._key:
             entries = self._entries()
             tensors = [t.detach() for _, t in entries]
-            _require_device_tensors(tensors, "RunStatistics")
+            require_device_tensors(tensors, "RunStatistics")
             self._tab = _device_table(tensors)
             self._key = key
             self._names = tuple(name for name, _ in entries)
