@@ -550,6 +550,27 @@ int locate_swd_project(const float* level, int N, int S, const int32_t* pos, int
 size_t locate_swd_distance_workspace_bytes(void);
 int locate_swd_distance(const float* a, const float* b, int64_t count, float* out, void* workspace, void* stream);
 
+/* ---- exact nearest neighbours in the 8-bit domain (csrc/neighbours.hip; locate_amd/neighbours.py).  Integers throughout: the
+ *      result depends on nothing but the bytes, no atomics.
+ *      Code of an image x fp32 [3, S, S], per element: t = fmul_rn(fadd_rn(x, 1), 127.5); u = 0 for t < 0, 255 for t > 255, else
+ *      rintf(t) (ties to even); code = u - 128 as int8.  A row holds the codes in c, y, x order in row_bytes = roundup(3 S^2, 64)
+ *      bytes (locate_nn_row_bytes; 0 for S outside 1 .. 4096), the pad bytes 0.  norms[i] = int64 sum of code^2; nonfinite[i] = the
+ *      number of NaN / Inf elements (their code byte is 0; an image with any is "flagged").  x 4-byte aligned (16-byte loads when it
+ *      is 16-byte aligned and 3 S^2 a multiple of 4), codes 16-byte aligned.
+ *      locate_nn_search: d2(q, r) = sum (code_q - code_r)^2 = norm_q + norm_r - 2 dot(q, r), the dot product on
+ *      v_mfma_i32_32x32x32_i8, rows longer than 65536 bytes in int32 segments added in int64.  Per query the k (1 .. 8) references
+ *      with the smallest (d2, index) in lexicographic order into d2 int64 [Q, k] / index int32 [Q, k]; empty slots (fewer than k
+ *      candidates) hold -1 / -1, as does every slot of a flagged query (qflags[i] != 0).  A reference with rflags[j] != 0 (rflags
+ *      may be null: none) is never returned, nor is reference skip[i] for query i (skip may be null; -1: none).  qcodes [Q, row_bytes],
+ *      rcodes [N, row_bytes], 16-byte aligned; row_bytes a multiple of 64, at most 262144; N < 2^30.  The norms must be those of the
+ *      rows.  `workspace`: locate_nn_search_workspace_bytes(Q, N, k) bytes, 8-byte aligned, need not be zeroed. ---- */
+int locate_nn_row_bytes(int S);
+int locate_nn_encode(const float* x, int n, int S, int8_t* codes, int64_t* norms, int32_t* nonfinite, void* stream);
+size_t locate_nn_search_workspace_bytes(int Q, int N, int k);
+int locate_nn_search(const int8_t* qcodes, const int64_t* qnorms, const int32_t* qflags, int Q, const int8_t* rcodes, const int64_t* rnorms,
+                     const int32_t* rflags, int N, int row_bytes, const int32_t* skip, int k, int64_t* d2, int32_t* index, void* workspace,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

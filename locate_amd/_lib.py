@@ -166,6 +166,10 @@ PROTOTYPES = {
     "locate_swd_project": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     "locate_swd_distance_workspace_bytes": (c_sz, []),
     "locate_swd_distance": (c_i, [c_p, c_p, c_i64, c_p, c_p, c_p]),
+    "locate_nn_row_bytes": (c_i, [c_i]),
+    "locate_nn_encode": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "locate_nn_search_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "locate_nn_search": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
 }
 
 
@@ -175,7 +179,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 14
+EXPECTED_ABI = 15
 
 
 _lib = None

@@ -6,7 +6,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
                              [--swd-images 0] [--ema-half-life 0] [--stats-every 0] [--dynamics-every 0]
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
-                             [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0]
+                             [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0] [--neighbours 0] [--neighbours-k 3]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -48,7 +48,11 @@ Differences from the reference, all additions:
   * `spill_every=` / `--spill-every N` (off by default; needs `--rollback-every`): once N iterations lie behind the last one, the
     committed snapshot goes to `OUT/spill/spill-K.bin` in the background (`locate_amd.spill`) - the training stream does not wait -
     and `--resume` continues from that file, bit for bit, when it is newer than the last `trainer.torch`: a killed job loses
-    minutes, not the epoch.  One pinned host buffer of a snapshot slot's size."""
+    minutes, not the epoch.  One pinned host buffer of a snapshot slot's size;
+  * `neighbours=` / `--neighbours IMAGES` (off by default): after every epoch the nearest training images of the sample picture's
+    images, exact in the 8-bit domain (`locate_amd.neighbours`): a record in `OUT/error/neighbours.json` and the picture
+    `OUT/error/{epoch}-neighbours.png` of rows [sample | its `--neighbours-k` nearest training images].  The evaluation has no side
+    effect on the training; the bank is one more copy of the training set's canonical views, as bytes, in device memory."""
 import argparse
 import json
 import os
@@ -198,13 +202,22 @@ class Trainer:
     `iterations`: from a spill through `restore_training_state`, with the host state restored exactly as trainer.torch's is; the
     choice goes into `out/error/resumes.json` as {"from": "spill" | "save", "iterations"}.  run() calls `spill.wait()` before it
     returns or re-raises, so a run that ends normally leaves no half-started writer.  Out of scope: data parallelism, compression,
-    an asynchronous save_state(), bit-exact graphed resumes (two warm-up iterations per resume, as today)."""
+    an asynchronous save_state(), bit-exact graphed resumes (two warm-up iterations per resume, as today).
+
+    neighbours: a `NearestNeighbours` whose reference is set, or None (the default: nothing below happens, and every file, record and
+    key is what it is without this argument).  After each epoch's SWD record, `neighbours.evaluate(gen, latents=sampler.fixed_noise)`
+    runs - the samples are the ones of the sample picture - and {"epoch", "iterations", "images", "k", "generated_to_real",
+    "generated_to_generated", "real_to_real", "real_among_themselves", "nonfinite", "index"} is appended to the list in
+    `out/error/neighbours.json` (a resumed run appends to the list it finds); `out/error/{e+1}-neighbours.png` shows every sample beside
+    its nearest training images.  With `average`, the same keys for the averaged generator go under "average" and its picture to
+    `{e+1}-neighbours.ema.png`.  The evaluation leaves weights, u / v and optimizer states untouched.  Under data parallelism only
+    rank 0 should be given one."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
-                 max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0):
+                 max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -236,6 +249,7 @@ class Trainer:
         self._latent_rng = None
         self.log = log
         self.swd = swd
+        self.neighbours = neighbours
         self.average = average
         self._ema_sampler = None
         if int(stats_every) < 0:
@@ -522,6 +536,26 @@ class Trainer:
             records[-1]["average"] = {"levels": value["levels"], "mean": value["mean"]}
         return _write_json(path, records)
 
+    def _nearest(self, e):
+        """One record of the samples' nearest training images into out/error/neighbours.json (written to a .tmp and renamed) and
+        the picture out/error/{e+1}-neighbours.png, for the sampler's fixed latents; returns the files written."""
+        keys = ("images", "k", "generated_to_real", "generated_to_generated", "real_to_real", "real_among_themselves", "nonfinite", "index")
+        latents = self.sampler.fixed_noise
+        value = self.neighbours.evaluate(self.gen, latents=latents)
+        path = os.path.join(self.out, "error", "neighbours.json")
+        records = []
+        if os.path.exists(path):
+            with open(path) as f:
+                records = json.load(f)
+        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **{k: value[k] for k in keys}))
+        written = [self.neighbours.save_picture(os.path.join(self.out, "error", "%d-neighbours.png" % (e + 1)), self.gen, latents=latents)]
+        if self.average is not None:
+            value = self.neighbours.evaluate(self.average.generator, latents=latents)
+            records[-1]["average"] = {k: value[k] for k in keys}
+            written.append(self.neighbours.save_picture(os.path.join(self.out, "error", "%d-neighbours.ema.png" % (e + 1)),
+                                                        self.average.generator, latents=latents))
+        return [_write_json(path, records)] + written
+
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
         returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
@@ -581,6 +615,8 @@ class Trainer:
                 self.written.append(self._save_guards(e + 1))         # raises, before the save below, if a guard is exhausted
             if self.swd is not None:
                 self.written.append(self._measure(e))
+            if self.neighbours is not None:
+                self.written += self._nearest(e)
             self.epoch, self.sub = e + 1, 0
             if self.stats is not None:
                 self._check_stats(before_save=True)
@@ -588,7 +624,8 @@ class Trainer:
         return self.iterations
 
 
-def main(argv=None):
+def parser():
+    """The command line's argument parser (needs no GPU)."""
     ap = argparse.ArgumentParser(prog="python -m locate_amd.run", description="Train on a prepared image store and watch the run.")
     ap.add_argument("--store", required=True, help="uint8 [N, H, W, 3] .npy file (locate_amd.data.prepare_folder)")
     ap.add_argument("--image-size", type=int, required=True)
@@ -631,7 +668,21 @@ def main(argv=None):
     ap.add_argument("--spill-every", type=int, default=0, metavar="N",
                     help="write the last-good copy to OUT/spill in the background once N iterations lie behind the last one, and let "
                          "--resume continue from it when it is newer than the last save; needs --rollback-every; 0: off")
+    ap.add_argument("--neighbours", type=int, default=0, metavar="IMAGES",
+                    help="after every epoch, the nearest training images of the sample picture's images, exact in the 8-bit domain "
+                         "(OUT/error/neighbours.json, OUT/error/EPOCH-neighbours.png), against baselines from IMAGES real images; "
+                         "one more copy of the training set's canonical views in device memory; 0: off")
+    ap.add_argument("--neighbours-k", type=int, default=3, metavar="K", help="nearest training images per sample, 1 .. 8")
+    return ap
+
+
+def main(argv=None):
+    ap = parser()
     args = ap.parse_args(argv)
+    if args.neighbours < 0:
+        ap.error("--neighbours must be >= 0")
+    if not 1 <= args.neighbours_k <= 8:
+        ap.error("--neighbours-k must be 1 .. 8")
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
     if args.dynamics_every < 0:
@@ -680,6 +731,11 @@ def main(argv=None):
         from .metric import SlicedWasserstein
         swd = SlicedWasserstein(args.image_size, images=args.swd_images, seed=args.seed, chunk=min(64, args.swd_images), device=dev)
         swd.reference_from_pipeline(pipeline)
+    neighbours = None
+    if args.neighbours > 0:
+        from .neighbours import NearestNeighbours
+        neighbours = NearestNeighbours(args.image_size, k=args.neighbours_k, images=args.neighbours, seed=args.seed, device=dev)
+        neighbours.reference_from_store(pipeline.store)
     average = None
     if args.ema_half_life > 0:
         from .average import AveragedGenerator
@@ -700,7 +756,7 @@ def main(argv=None):
                       seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average, stats=stats,
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
-                      dynamics=dynamics, dynamics_every=args.dynamics_every,
+                      dynamics=dynamics, dynamics_every=args.dynamics_every, neighbours=neighbours,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
