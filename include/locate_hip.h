@@ -571,6 +571,19 @@ int locate_nn_search(const int8_t* qcodes, const int64_t* qnorms, const int32_t*
                      const int32_t* rflags, int N, int row_bytes, const int32_t* skip, int k, int64_t* d2, int32_t* index, void* workspace,
                      void* stream);
 
+/* ---- "which balls is each query in": the counts behind precision / recall / density / coverage (csrc/neighbours.hip;
+ *      locate_amd/manifold.py).  The conventions, the distances and the limits of locate_nn_search.  The pair (q, r) counts iff
+ *      qflags[q] == 0, rflags[r] == 0 (rflags may be null: none flagged), radius2[r] >= 0 (a negative radius: this reference has no
+ *      ball), r != skip[q] (skip may be null; -1: none) and d2(q, r) <= radius2[r], compared in int64.  hits int32 [Q]: the counting
+ *      pairs of each query; covered int32 [N]: those of each reference - may be null: then no work and no workspace for it.  Two
+ *      launches, no atomics: every block writes its counts, a second kernel adds them in ascending tile order; two calls give the
+ *      same words.  radius2 int64 [N], 8-byte aligned.  `workspace`: locate_nn_within_workspace_bytes(Q, N, covered != null) bytes,
+ *      4-byte aligned; neither it nor the outputs need be zeroed. ---- */
+size_t locate_nn_within_workspace_bytes(int Q, int N, int want_covered);
+int locate_nn_within(const int8_t* qcodes, const int64_t* qnorms, const int32_t* qflags, int Q, const int8_t* rcodes, const int64_t* rnorms,
+                     const int32_t* rflags, int N, int row_bytes, const int64_t* radius2, const int32_t* skip, int32_t* hits, int32_t* covered,
+                     void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

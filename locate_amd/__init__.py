@@ -15,6 +15,7 @@ from .monitor import LossHistory, Sampler, image_grid  # noqa: F401
 from .metric import (SlicedWasserstein, descriptor_stats, laplacian_pyramid, project_descriptors, pyramid_levels,  # noqa: F401
                      sorted_distance)
 from .neighbours import NearestNeighbours, encode_images, nearest  # noqa: F401
+from .manifold import ManifoldMetrics, kth_radius, within  # noqa: F401
 from .average import AveragedGenerator, average_weight  # noqa: F401
 from .stats import NonFiniteError, RunStatistics, tensor_statistics  # noqa: F401
 from .dynamics import RunDynamics, tensor_deltas  # noqa: F401

@@ -6,6 +6,9 @@
 //               with the dot product on v_mfma_i32_32x32x32_i8 - integers throughout, so the Gram form is EXACT and the result
 //               depends on nothing but the bytes.  Two launches: a tile kernel that walks whole rows and leaves each query's best
 //               of the tile in the workspace, and a merge.  No atomics.
+//   nn_within : per query the number of references whose ball it lies in (d2 <= radius2[r]), per reference the number of queries
+//               in its ball - the counts behind precision / recall / density / coverage.  The same tile walk with a lighter end:
+//               a comparison per pair, counts per block in the workspace, and a sum.  No atomics here either.
 // Order: key = d2 * 2^30 + index as an unsigned 64-bit word - the lexicographic order of (d2, index) and the tie rule (lower index
 // first) in one comparison.  index < 2^30 and d2 <= 255^2 row_bytes < 2^34 for rows up to NN_ROW_MAX bytes; the all-ones word is
 // larger than every key and marks an empty slot.
@@ -133,16 +136,17 @@ __device__ __forceinline__ void nn_insert(nn_key (&best)[NN_KMAX], nn_key x) {
 // before the matrix instructions of stage s - 1 and written to LDS after them, one barrier per stage.  Rows are a multiple of 64
 // bytes, not of 128: the last stage's upper half is zero on both sides.  Rows beyond N and Q are zero and masked at the end.
 // SEGMENTED (rows longer than NN_SEGMENT bytes): the int32 accumulators are added into int64 sums every 512 stages.
+#define NN_SMEM_BYTES (2 * (NN_TR + NN_TQ) * NN_LD)          // 55296 bytes: two blocks per CU
+
+// The stage loop, once, for every kernel over the block tile.  It leaves the dot products of the block's 128 x 64 pairs in
+// registers - sum[j][e] + acc[j][e], or acc[j][e] alone when not SEGMENTED - and ends on a barrier, so the caller may reuse
+// smem at once.
 template <bool SEGMENTED>
-__global__ __launch_bounds__(NN_THREADS, 2) void nn_tile_kernel(const int8_t* __restrict__ qcodes, const long long* __restrict__ qnorms, const int* __restrict__ qflags,
-                                                                int Q, const int8_t* __restrict__ rcodes, const long long* __restrict__ rnorms,
-                                                                const int* __restrict__ rflags, int N, int row_bytes, const int* __restrict__ skip, int k,
-                                                                nn_key* __restrict__ ws, int tiles) {
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * (NN_TR + NN_TQ) * NN_LD];          // 55296 bytes: two blocks per CU
+__device__ __forceinline__ void nn_tile_dots(const int8_t* __restrict__ qcodes, int Q, int q0, const int8_t* __restrict__ rcodes, int N, int r0, int row_bytes,
+                                             unsigned char* smem, i32x16 (&acc)[2], long long (&sum)[2][SEGMENTED ? 16 : 1]) {
     unsigned char* Rs = smem;                                  // [2][NN_TR][NN_LD]
     unsigned char* Qs = smem + 2 * NN_TR * NN_LD;              // [2][NN_TQ][NN_LD]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lrow = lane & 31, lhalf = lane >> 5;
-    const int r0 = blockIdx.x * NN_TR, q0 = blockIdx.y * NN_TQ;
     const int stages = (row_bytes + NN_STAGE - 1) / NN_STAGE;
     // fill: thread t owns the 16 bytes at (t & 7) 16 of rows (t >> 3) + 32 i - eight lanes read 128 consecutive bytes of a row
     const int crow = tid >> 3, cbyte = (tid & 7) * 16;
@@ -153,8 +157,6 @@ __global__ __launch_bounds__(NN_THREADS, 2) void nn_tile_kernel(const int8_t* __
 #pragma unroll
     for (int i = 0; i < 2; ++i) qsrc[i] = q0 + crow + 32 * i < Q ? qcodes + (size_t)(q0 + crow + 32 * i) * row_bytes + cbyte : nullptr;
 
-    i32x16 acc[2];
-    long long sum[2][SEGMENTED ? 16 : 1];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -203,6 +205,19 @@ __global__ __launch_bounds__(NN_THREADS, 2) void nn_tile_kernel(const int8_t* __
         }
         __syncthreads();
     }
+}
+
+template <bool SEGMENTED>
+__global__ __launch_bounds__(NN_THREADS, 2) void nn_tile_kernel(const int8_t* __restrict__ qcodes, const long long* __restrict__ qnorms, const int* __restrict__ qflags,
+                                                                int Q, const int8_t* __restrict__ rcodes, const long long* __restrict__ rnorms,
+                                                                const int* __restrict__ rflags, int N, int row_bytes, const int* __restrict__ skip, int k,
+                                                                nn_key* __restrict__ ws, int tiles) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[NN_SMEM_BYTES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lrow = lane & 31, lhalf = lane >> 5;
+    const int r0 = blockIdx.x * NN_TR, q0 = blockIdx.y * NN_TQ;
+    i32x16 acc[2];
+    long long sum[2][SEGMENTED ? 16 : 1];
+    nn_tile_dots<SEGMENTED>(qcodes, Q, q0, rcodes, N, r0, row_bytes, smem, acc, sum);
 
     // d2 and this lane's best per query.  A reference is a candidate if it exists, is not flagged and is not the query's `skip`;
     // a flagged query has no candidates.
@@ -312,5 +327,127 @@ LOCATE_API int locate_nn_search(const int8_t* qcodes, const int64_t* qnorms, con
     LOCATE_LAUNCH_CHECK("locate_nn_search (tiles)");
     nn_merge_kernel<<<Q, NN_MERGE_THREADS, 0, st>>>(ws, tiles, k, reinterpret_cast<long long*>(d2), index);
     LOCATE_LAUNCH_CHECK("locate_nn_search");
+    return LOCATE_OK;
+}
+
+// ---- which balls is each query in ----------------------------------------------------------------------------------------------
+// The pair (q, r) counts if q is not flagged, r exists, is not flagged, has a ball (radius2[r] >= 0) and is not the query's `skip`,
+// and d2 <= radius2[r] in int64.  A lane holds 2 x 16 such booleans.
+//   per query     : a lane adds its 16; the 8 lane groups (4 waves x 2 halves) meet in the staging LDS and thread t adds them for
+//                   query t - as the search does with its lists;
+//   per reference : a reference row lives in one wave - element e of the lanes of one half - so the wave's ballot of element e
+//                   holds the row of half 0 in its low word and the row of half 1 in its high word, for both query tiles: four
+//                   popcounts, no LDS.  Lane 16 h + e keeps the count of element e, half h, and stores it.
+// Each block writes its counts to hits_ws [Q][tiles_r] and cov_ws [N][tiles_q]; every word of both is written.
+template <bool SEGMENTED>
+__global__ __launch_bounds__(NN_THREADS, 2) void nn_within_kernel(const int8_t* __restrict__ qcodes, const long long* __restrict__ qnorms, const int* __restrict__ qflags,
+                                                                  int Q, const int8_t* __restrict__ rcodes, const long long* __restrict__ rnorms,
+                                                                  const int* __restrict__ rflags, int N, int row_bytes, const long long* __restrict__ radius2,
+                                                                  const int* __restrict__ skip, int* __restrict__ hits_ws, int tiles_r,
+                                                                  int* __restrict__ cov_ws, int tiles_q) {
+    __shared__ __attribute__((aligned(16))) unsigned char smem[NN_SMEM_BYTES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lrow = lane & 31, lhalf = lane >> 5;
+    const int r0 = blockIdx.x * NN_TR, q0 = blockIdx.y * NN_TQ;
+    i32x16 acc[2];
+    long long sum[2][SEGMENTED ? 16 : 1];
+    nn_tile_dots<SEGMENTED>(qcodes, Q, q0, rcodes, N, r0, row_bytes, smem, acc, sum);
+
+    long long rn[16], rad[16];
+    bool rok[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const int r = r0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * lhalf;
+        rn[e] = r < N ? rnorms[r] : 0;
+        rad[e] = r < N ? radius2[r] : -1;
+        rok[e] = r < N && (rflags == nullptr || rflags[r] == 0) && rad[e] >= 0;
+    }
+    bool in[2][16];
+    int* counts = reinterpret_cast<int*>(smem);          // [8 lane groups][NN_TQ]
+    const int group = 2 * wave + lhalf;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int q = q0 + 32 * j + lrow;
+        const bool qok = q < Q && qflags[q] == 0;
+        const long long nq = q < Q ? qnorms[q] : 0;
+        const int sk = (skip != nullptr && q < Q) ? skip[q] : -1;
+        int mine = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int r = r0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * lhalf;
+            const long long dot = SEGMENTED ? sum[j][SEGMENTED ? e : 0] + acc[j][e] : (long long)acc[j][e];
+            const long long d2 = nq + rn[e] - 2 * dot;
+            in[j][e] = qok && rok[e] && r != sk && d2 <= rad[e];
+            mine += in[j][e] ? 1 : 0;
+        }
+        counts[group * NN_TQ + 32 * j + lrow] = mine;
+    }
+    if (cov_ws != nullptr) {          // the same for every lane of the grid: the ballots below are of whole waves
+        int kept = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const unsigned long long b0 = __ballot(in[0][e]), b1 = __ballot(in[1][e]);
+            const int lo = __popc((unsigned)b0) + __popc((unsigned)b1);
+            const int hi = __popc((unsigned)(b0 >> 32)) + __popc((unsigned)(b1 >> 32));
+            if ((lane & 15) == e) kept = (lane & 16) ? hi : lo;
+        }
+        const int e = lane & 15, h = (lane >> 4) & 1;
+        const int r = r0 + 32 * wave + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (lane < 32 && r < N) cov_ws[(size_t)r * tiles_q + blockIdx.y] = kept;
+    }
+    __syncthreads();
+    if (tid < NN_TQ && q0 + tid < Q) {
+        int total = 0;
+#pragma unroll
+        for (int g = 0; g < 8; ++g) total += counts[g * NN_TQ + tid];
+        hits_ws[(size_t)(q0 + tid) * tiles_r + blockIdx.x] = total;
+    }
+}
+
+// one thread per output word: the first Q add a query's tiles, the next N (if wanted) a reference's, in ascending tile order
+__global__ __launch_bounds__(NN_THREADS) void nn_within_sum_kernel(const int* __restrict__ hits_ws, int Q, int tiles_r, int* __restrict__ hits,
+                                                                   const int* __restrict__ cov_ws, int N, int tiles_q, int* __restrict__ covered) {
+    const long long i = (long long)blockIdx.x * NN_THREADS + threadIdx.x;
+    const bool query = i < Q;
+    if (!query && (cov_ws == nullptr || i - Q >= N)) return;
+    const int* in = query ? hits_ws + (size_t)i * tiles_r : cov_ws + (size_t)(i - Q) * tiles_q;
+    const int tiles = query ? tiles_r : tiles_q;
+    int total = 0;
+    for (int t = 0; t < tiles; ++t) total += in[t];
+    if (query) hits[i] = total;
+    else covered[i - Q] = total;
+}
+
+LOCATE_API size_t locate_nn_within_workspace_bytes(int Q, int N, int want_covered) {
+    if (Q < 1 || N < 1) return 0;
+    const size_t per_query = (size_t)Q * (size_t)cdiv64(N, NN_TR) * sizeof(int32_t);
+    return per_query + (want_covered ? (size_t)N * (size_t)cdiv64(Q, NN_TQ) * sizeof(int32_t) : 0);
+}
+
+LOCATE_API int locate_nn_within(const int8_t* qcodes, const int64_t* qnorms, const int32_t* qflags, int Q, const int8_t* rcodes, const int64_t* rnorms,
+                                const int32_t* rflags, int N, int row_bytes, const int64_t* radius2, const int32_t* skip, int32_t* hits, int32_t* covered,
+                                void* workspace, void* stream) {
+    LOCATE_REQUIRE(qcodes && qnorms && qflags && rcodes && rnorms && radius2 && hits && workspace, "locate_nn_within: null pointer");
+    LOCATE_REQUIRE(Q >= 1 && Q <= NN_TQ * 65535, "locate_nn_within: Q = %d", Q);
+    LOCATE_REQUIRE(N >= 1 && (int64_t)N < ((int64_t)1 << NN_INDEX_BITS), "locate_nn_within: N = %d (1 .. 2^30 - 1)", N);
+    LOCATE_REQUIRE(row_bytes >= 64 && row_bytes % 64 == 0 && row_bytes <= NN_ROW_MAX, "locate_nn_within: row_bytes = %d (a multiple of 64 up to %d)", row_bytes,
+                   NN_ROW_MAX);
+    LOCATE_REQUIRE((((uintptr_t)qcodes | (uintptr_t)rcodes) & 15) == 0, "locate_nn_within: the code banks must be 16-byte aligned");
+    LOCATE_REQUIRE((((uintptr_t)qnorms | (uintptr_t)rnorms | (uintptr_t)radius2) & 7) == 0, "locate_nn_within: norms and radius2 must be 8-byte aligned");
+    LOCATE_REQUIRE((((uintptr_t)qflags | (uintptr_t)rflags | (uintptr_t)skip | (uintptr_t)hits | (uintptr_t)covered | (uintptr_t)workspace) & 3) == 0,
+                   "locate_nn_within: flags, skip, hits, covered and workspace must be 4-byte aligned");
+    const int tiles_r = (int)cdiv64(N, NN_TR), tiles_q = (int)cdiv64(Q, NN_TQ);
+    const dim3 grid((unsigned)tiles_r, (unsigned)tiles_q);
+    hipStream_t st = as_stream(stream);
+    int* hits_ws = static_cast<int*>(workspace);
+    int* cov_ws = covered ? hits_ws + (size_t)Q * tiles_r : nullptr;
+    const long long* qn = reinterpret_cast<const long long*>(qnorms);
+    const long long* rn = reinterpret_cast<const long long*>(rnorms);
+    const long long* rad = reinterpret_cast<const long long*>(radius2);
+    if (row_bytes > NN_SEGMENT) nn_within_kernel<true><<<grid, NN_THREADS, 0, st>>>(qcodes, qn, qflags, Q, rcodes, rn, rflags, N, row_bytes, rad, skip, hits_ws, tiles_r, cov_ws, tiles_q);
+    else nn_within_kernel<false><<<grid, NN_THREADS, 0, st>>>(qcodes, qn, qflags, Q, rcodes, rn, rflags, N, row_bytes, rad, skip, hits_ws, tiles_r, cov_ws, tiles_q);
+    LOCATE_LAUNCH_CHECK("locate_nn_within (tiles)");
+    const long long words = (long long)Q + (covered ? N : 0);
+    nn_within_sum_kernel<<<(unsigned)cdiv64(words, NN_THREADS), NN_THREADS, 0, st>>>(hits_ws, Q, tiles_r, hits, cov_ws, N, tiles_q, covered);
+    LOCATE_LAUNCH_CHECK("locate_nn_within");
     return LOCATE_OK;
 }

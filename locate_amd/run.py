@@ -7,6 +7,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--swd-images 0] [--ema-half-life 0] [--stats-every 0] [--dynamics-every 0]
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
                              [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0] [--neighbours 0] [--neighbours-k 3]
+                             [--manifold 0] [--manifold-k 3]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -52,7 +53,11 @@ Differences from the reference, all additions:
   * `neighbours=` / `--neighbours IMAGES` (off by default): after every epoch the nearest training images of the sample picture's
     images, exact in the 8-bit domain (`locate_amd.neighbours`): a record in `OUT/error/neighbours.json` and the picture
     `OUT/error/{epoch}-neighbours.png` of rows [sample | its `--neighbours-k` nearest training images].  The evaluation has no side
-    effect on the training; the bank is one more copy of the training set's canonical views, as bytes, in device memory."""
+    effect on the training; the bank is one more copy of the training set's canonical views, as bytes, in device memory;
+  * `manifold=` / `--manifold IMAGES` (off by default): after every epoch precision, recall, density and coverage of IMAGES
+    generated samples against IMAGES real images (`locate_amd.manifold`, `--manifold-k` neighbours per ball), exact in the 8-bit
+    domain, with a real-against-real baseline: a record in `OUT/error/manifold.json`.  It tells lost modes from lost quality.  The
+    evaluation has no side effect on the training; under data parallelism only rank 0 evaluates."""
 import argparse
 import json
 import os
@@ -211,13 +216,20 @@ class Trainer:
     `out/error/neighbours.json` (a resumed run appends to the list it finds); `out/error/{e+1}-neighbours.png` shows every sample beside
     its nearest training images.  With `average`, the same keys for the averaged generator go under "average" and its picture to
     `{e+1}-neighbours.ema.png`.  The evaluation leaves weights, u / v and optimizer states untouched.  Under data parallelism only
-    rank 0 should be given one."""
+    rank 0 should be given one.
+
+    manifold: a `ManifoldMetrics` whose reference is set, or None (the default: nothing below happens, and every file, record and
+    key is what it is without this argument).  After each epoch's neighbours record, `manifold.evaluate(gen)` runs on the metric's own
+    fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/manifold.json` (written to a
+    .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record - without the
+    baseline, which is the same - goes under "average".  The evaluation leaves weights, u / v and optimizer states untouched.
+    Under data parallelism only rank 0 should be given one."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
-                 max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None):
+                 max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None, manifold=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -250,6 +262,7 @@ class Trainer:
         self.log = log
         self.swd = swd
         self.neighbours = neighbours
+        self.manifold = manifold
         self.average = average
         self._ema_sampler = None
         if int(stats_every) < 0:
@@ -556,6 +569,21 @@ class Trainer:
                                                         self.average.generator, latents=latents))
         return [_write_json(path, records)] + written
 
+    def _manifold(self, e):
+        """One record of precision / recall / density / coverage into out/error/manifold.json (written to a .tmp and renamed), for
+        the metric's own fixed latents; returns the file written."""
+        value = self.manifold.evaluate(self.gen)
+        path = os.path.join(self.out, "error", "manifold.json")
+        records = []
+        if os.path.exists(path):
+            with open(path) as f:
+                records = json.load(f)
+        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
+        if self.average is not None:
+            value = self.manifold.evaluate(self.average.generator)
+            records[-1]["average"] = {k: v for k, v in value.items() if k != "baseline"}
+        return _write_json(path, records)
+
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
         returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
@@ -617,6 +645,8 @@ class Trainer:
                 self.written.append(self._measure(e))
             if self.neighbours is not None:
                 self.written += self._nearest(e)
+            if self.manifold is not None:
+                self.written.append(self._manifold(e))
             self.epoch, self.sub = e + 1, 0
             if self.stats is not None:
                 self._check_stats(before_save=True)
@@ -673,6 +703,10 @@ def parser():
                          "(OUT/error/neighbours.json, OUT/error/EPOCH-neighbours.png), against baselines from IMAGES real images; "
                          "one more copy of the training set's canonical views in device memory; 0: off")
     ap.add_argument("--neighbours-k", type=int, default=3, metavar="K", help="nearest training images per sample, 1 .. 8")
+    ap.add_argument("--manifold", type=int, default=0, metavar="IMAGES",
+                    help="after every epoch, precision, recall, density and coverage of IMAGES generated samples against IMAGES real "
+                         "images, exact in the 8-bit domain, with a real-against-real baseline (OUT/error/manifold.json); 0: off")
+    ap.add_argument("--manifold-k", type=int, default=3, metavar="K", help="a ball reaches to the K-th nearest other image, 1 .. 8")
     return ap
 
 
@@ -683,6 +717,10 @@ def main(argv=None):
         ap.error("--neighbours must be >= 0")
     if not 1 <= args.neighbours_k <= 8:
         ap.error("--neighbours-k must be 1 .. 8")
+    if args.manifold < 0:
+        ap.error("--manifold must be >= 0")
+    if not 1 <= args.manifold_k <= 8:
+        ap.error("--manifold-k must be 1 .. 8")
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
     if args.dynamics_every < 0:
@@ -736,6 +774,12 @@ def main(argv=None):
         from .neighbours import NearestNeighbours
         neighbours = NearestNeighbours(args.image_size, k=args.neighbours_k, images=args.neighbours, seed=args.seed, device=dev)
         neighbours.reference_from_store(pipeline.store)
+    manifold = None
+    if args.manifold > 0:
+        from .manifold import ManifoldMetrics
+        manifold = ManifoldMetrics(args.image_size, k=args.manifold_k, images=args.manifold, seed=args.seed, chunk=min(64, args.manifold),
+                                   device=dev)
+        manifold.reference_from_store(pipeline.store)
     average = None
     if args.ema_half_life > 0:
         from .average import AveragedGenerator
@@ -756,7 +800,7 @@ def main(argv=None):
                       seed=args.seed, diters=args.diters, graphed=args.graph, log=log, swd=swd, average=average, stats=stats,
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
-                      dynamics=dynamics, dynamics_every=args.dynamics_every, neighbours=neighbours,
+                      dynamics=dynamics, dynamics_every=args.dynamics_every, neighbours=neighbours, manifold=manifold,
                       sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
