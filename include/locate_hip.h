@@ -476,6 +476,51 @@ size_t locate_dyn_workspace_bytes(int n_chunks);
 int locate_dyn_pass(const void* tensors, const void* chunks, int n_tensors, int n_chunks, int mode, void* records, void* workspace,
                     void* stream);
 
+/* ---- what a reduced-precision format would do to a contraction operand (no reference counterpart; locate_amd/formats.py).
+ *      host_views: HOST array of n_views (1 .. locate_formats_max_views() = 8) records {const float* x; int32 B, C, P; int64
+ *      batch_stride; int32 axis} (natural C layout, locate_formats_view_record_bytes() = 40): element (b, c, p) at
+ *      x[b * batch_stride + c * P + p]; the 32-element scale blocks run along c (axis 1: 32 consecutive c at fixed (b, p)) or
+ *      along p (axis 2: 32 consecutive p at fixed (b, c)), a line's last block covers the members that exist.  x: DEVICE fp32,
+ *      4-byte aligned; fewer than 2^31 elements.  The records travel by value in the launch arguments: no device table.
+ *      rows: DEVICE slots of locate_formats_base_record_bytes() + locate_formats_count() * locate_formats_format_record_bytes()
+ *      = 304 + 5 * 32 = 464 bytes, 8-byte aligned; view i ADDS into slot row_slots[i] (HOST array; no two views of a call share
+ *      a slot; the caller zeroes a slot before its first call):
+ *        base    uint64 n           elements
+ *                uint64 zeros       +-0 elements
+ *                uint64 nonfinite   NaN and +-Inf elements: counted here and left out of everything else
+ *                uint64 calls       calls added into this slot
+ *                double sumsq       sum of (double) x * (double) x over the finite elements (exact squares)
+ *                uint32 absmax      bit pattern of the largest finite magnitude (over calls: the maximum); uint32 pad
+ *                uint64 hist[32]    finite non-zero elements by fp32 exponent field (0 counted as 1): bin j lies j below the
+ *                                   field of THIS CALL's absmax, bin 31 takes everything lower
+ *        format  double err_sumsq   sum of e * e, e = (double) x - (double) q * 2^-scale in double (exact squares)
+ *                uint64 flushed     x finite and non-zero, q == 0
+ *                uint64 subnormal   q != 0 and |q| below the grid's smallest normal
+ *                uint64 clamped     the rounded magnitude exceeded the grid's maximum (q is then the maximum)
+ *      Formats (locate_formats_name(i)), every one rounded to nearest even onto its grid, subnormals included:
+ *        0 e4m3_tensor  3 mantissa bits, smallest normal 2^-6, max 448; one 2^k per tensor, absmax * 2^k in [2^7, 2^8) (the
+ *                       rule of the fp8 contractions); v_cvt_pk_fp8_f32 / v_cvt_f32_fp8
+ *        1 e5m2_tensor  2, 2^-14, 57344; one 2^k per tensor, absmax * 2^k in [2^14, 2^15); v_cvt_pk_bf8_f32 / v_cvt_f32_bf8
+ *        2 mxfp8_e4m3   grid of 0; per scale block 2^X, X = clamp(max(field(A), 1) - 127 - 8, -127, 127), A the block's largest
+ *                       finite magnitude (OCP MX v1.0)
+ *        3 mxfp4_e2m1   1, 2^0, 6; the same with - 2
+ *        4 bf16         7, 2^-126, largest finite bf16; no scale
+ *      workspace: DEVICE, locate_formats_workspace_bytes(host_views, n_views) bytes (0 for damaged views), 8-byte aligned, need
+ *      not be zeroed.  A view's contribution depends only on its contents and (B, C, P, axis) - not on alignment, batch_stride,
+ *      the other views or the grid: two calls give the same bits.  Four launches (a grid pass and a one-block-per-view sum,
+ *      twice: the per-tensor scales need absmax first, which the second pass reads from the workspace); no floating-point
+ *      atomics, no allocation, host read or synchronisation: legal under stream capture.  Damaged arguments (n_views out of
+ *      range, axis not 1 or 2, a non-positive extent, batch_stride below C * P, a misaligned or null address, a shared or
+ *      negative slot) return an error status and launch nothing. ---- */
+int locate_formats_count(void);
+const char* locate_formats_name(int i);          /* NULL outside [0, locate_formats_count()) */
+int locate_formats_max_views(void);
+size_t locate_formats_view_record_bytes(void);
+size_t locate_formats_base_record_bytes(void);
+size_t locate_formats_format_record_bytes(void);
+size_t locate_formats_workspace_bytes(const void* host_views, int n_views);
+int locate_formats_audit(const void* host_views, int n_views, const int* row_slots, void* rows, void* workspace, void* stream);
+
 /* ---- loss glue (main.py:149-156,164-169, libs/utils.py:133-134, libs/grad_penalty.py:1-2): values and the
  *      gradients w.r.t. the discriminator outputs ---- */
 int locate_d_loss(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, float* losses,

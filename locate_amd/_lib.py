@@ -150,6 +150,14 @@ PROTOTYPES = {
     "locate_dyn_max_blocks": (c_i, []),
     "locate_dyn_workspace_bytes": (c_sz, [c_i]),
     "locate_dyn_pass": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    "locate_formats_count": (c_i, []),
+    "locate_formats_name": (ctypes.c_char_p, [c_i]),
+    "locate_formats_max_views": (c_i, []),
+    "locate_formats_view_record_bytes": (c_sz, []),
+    "locate_formats_base_record_bytes": (c_sz, []),
+    "locate_formats_format_record_bytes": (c_sz, []),
+    "locate_formats_workspace_bytes": (c_sz, [c_p, c_i]),
+    "locate_formats_audit": (c_i, [c_p, c_i, c_p, c_p, c_p, c_p]),
     "locate_d_loss": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_p, c_p]),
     "locate_g_loss": (c_i, [c_p, c_i, c_p, c_p, c_p]),
     "locate_input_param_record_bytes": (c_sz, []),
@@ -181,7 +189,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 16
+EXPECTED_ABI = 17
 
 
 _lib = None

@@ -1369,10 +1369,19 @@ def _win_ws_bytes(geom, garr, adjfmt):
     return hit
 
 
+# The tap of the format audit (locate_amd/formats.py): None, or a callable (role, weight, operand, second operand, forward_of_r)
+# that is handed the operands of every DENSE contraction before it is issued - role "fwd" / "dgrad" with the gathered operand (and
+# None), "wgrad" with the layer's input and its output gradient.  It reads and writes nothing of the step's; with None every launch,
+# argument and allocation is what it is without this line.
+CONTRACTION_TAP = None
+
+
 def _contract(forward_of_r, x, w, owner, spec, geom, garr, sigma, bias, y, precision=0, amax=None, epilogue=None):
     """y = R(x) (forward_of_r) or R^T(x), times 1/sigma, plus bias - dispatched on the layer's grouping mode.
     amax: x's largest-magnitude word, if its producer left one (fp16-piece form, panel format bit 2).
     epilogue: _ActEpilogue (regular direction on a 1x1 map only) - RootTanh(y) written as a second output."""
+    if CONTRACTION_TAP is not None and spec.mode == "dense":
+        CONTRACTION_TAP("fwd" if forward_of_r == (spec.kind == "conv") else "dgrad", w, x, None, forward_of_r)
     L = lib()
     st = _stream()
     _, sbg, sst, inv_sigma = _sigma_args(sigma, x.shape[0])
@@ -1455,10 +1464,13 @@ def _conv_input_grad(gy, x_like, w, owner, spec, geom, garr, sigma, precision=0,
 
 
 def _raw_weight_grad(spec, geom, garr, xin, gout, gw, w_ref, inv_sigma, sbg, sst, partial, precision=0, amax_in=None, amax_out=None,
-                     rt=None, group_dots=0):
+                     rt=None, group_dots=0, w_key=None):
     """gw = (sum over the batch of R's input x R's output gradient) / sigma, plus the partial sums of <G, W_bar>.
     With a runtime that defers its finalisers, the layers on 1x1 maps / with one output pixel are only queued: one launch for
-    all of them at the end of the pass (Runtime.queue_small_wgrad)."""
+    all of them at the end of the pass (Runtime.queue_small_wgrad).
+    w_key: the layer's weight where w_ref is None (the tap's key; read by nothing else)."""
+    if CONTRACTION_TAP is not None and spec.mode == "dense":          # before the deferral: a queued layer's operands are audited too
+        CONTRACTION_TAP("wgrad", w_ref if w_ref is not None else w_key, *((xin, gout) if spec.kind == "conv" else (gout, xin)), True)
     L = lib()
     st = _stream()
     if spec.mode == "dense" and rt is not None and rt.defer_finalisers:
@@ -1533,7 +1545,7 @@ def _conv_weight_grad(rt, x, gy, y, bias, w, u_param, v_param, sigma, wv, spec, 
             dsig = rt.defer_dv(v_param, u_param, w, h, wd) if need_v else None
             rt.queue_sn_rank1(partial, npg, groups, sigma, sigma.stride(0), u, v, wv, wv.stride(0), gw, gu, dsig, h, wd)
             return gw, gu
-        _raw_weight_grad(spec, geom, garr, xin, gout, gw, None, inv_sigma, sbg, sst, None, rt.precision, am_in, am_out, rt)
+        _raw_weight_grad(spec, geom, garr, xin, gout, gw, None, inv_sigma, sbg, sst, None, rt.precision, am_in, am_out, rt, w_key=w)
         dsig = rt.defer_dv(v_param, u_param, w, h, wd) if need_v else None
         Bn, Mn = gy.shape[0], gy.shape[1]
         plane = gy.numel() // (Bn * Mn)

@@ -4,7 +4,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
 
     python -m locate_amd.run --store FILE.npy --image-size S --batch B --out DIR [--epochs N] [--max-iterations N]
                              [--images 64] [--seed 999] [--minibatches 8] [--diters 1] [--graph] [--resume] [--keep-spectral-norm]
-                             [--swd-images 0] [--ema-half-life 0] [--stats-every 0] [--dynamics-every 0]
+                             [--swd-images 0] [--ema-half-life 0] [--stats-every 0] [--dynamics-every 0] [--formats-every 0]
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
                              [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0] [--neighbours 0] [--neighbours-k 3]
                              [--manifold 0] [--manifold-k 3]
@@ -36,6 +36,10 @@ Differences from the reference, all additions:
   * `dynamics=` / `--dynamics-every N` (off by default): around every N-th iteration, per tensor the update-to-weight ratio
     |dw| / |w| of that one iteration and per spectrally normalised layer the sigma its forward divides by beside its top singular
     value (`locate_amd.dynamics`), by launches beside the training step; `OUT/error/{epoch}-dynamics.npz` holds an epoch's records;
+  * `formats=` / `--formats-every N` (off by default; eager runs only - not with `--graph`): every N-th iteration the operands of
+    every dense contraction - gathered activations, output gradients, weights - are audited against five candidate number formats
+    (`locate_amd.formats`): what each would flush, push into its subnormals or clamp, and the signal-to-noise ratio left;
+    `OUT/error/{epoch}-formats.npz` holds an epoch's records;
   * `--clip-grad-norm X` / `--no-skip-nonfinite` (without either, nothing below happens): both networks are stepped by
     `GuardedNadam` (`locate_amd.guard`) instead of `Nadam`: a step whose gradients hold a NaN or an Inf is skipped on the device
     (unless `--no-skip-nonfinite`), and with X > 0 the gradients are scaled down to the global norm X.  `OUT/error/{epoch}-guard.json`
@@ -171,6 +175,14 @@ class Trainer:
     graphed=True the iteration that builds the graphs runs its two warm-up iterations too: a record around it spans all three.
     Under data parallelism only rank 0 needs one.
 
+    formats: a `FormatAudit` over step.gen and step.dis, or None (the default: nothing below happens, and every file, record and
+    key is what it is without this argument); `formats_every`: N >= 0, 0 (the default) is off.  The iteration that makes
+    `iterations` a multiple of N runs inside `formats.iteration(iterations)`: the operands of its dense contractions are audited
+    against the candidate number formats (`locate_amd.formats`) by launches that only read them, and the cost falls on that
+    iteration only.  `out/error/{e+1}-formats.npz` (`FormatAudit.save`) is written beside `{e+1}-dynamics.npz` and holds the
+    records of that epoch taken by this call of run().  Nothing goes into trainer.torch.  A replayed graph runs no Python, so
+    graphed=True with formats_every > 0 raises ValueError.  Under data parallelism only rank 0 needs one.
+
     Guarded optimizers: where step.gen_opt or step.dis_opt is a `GuardedNadam` (anything with `counters()`; with plain `Nadam`s
     nothing below happens, and every file, record and key is what it is today), its counters are read where this loop reads from
     the device anyway - with the progress line - and before every save_state().  An optimizer whose `consecutive_skips` has reached
@@ -229,7 +241,8 @@ class Trainer:
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
-                 max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None, manifold=None):
+                 max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None, manifold=None,
+                 formats=None, formats_every=0):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -271,6 +284,12 @@ class Trainer:
         if int(dynamics_every) < 0:
             raise ValueError("dynamics_every must be >= 0, got %r" % (dynamics_every,))
         self.dynamics, self.dynamics_every = dynamics, int(dynamics_every)
+        if int(formats_every) < 0:
+            raise ValueError("formats_every must be >= 0, got %r" % (formats_every,))
+        if self.graphed and int(formats_every) > 0:
+            raise ValueError("graphed=True with formats_every > 0: a replayed graph runs no Python, so the audit's tap sees no "
+                             "contraction; audit an eager run")
+        self.formats, self.formats_every = formats, int(formats_every)
         if int(max_consecutive_skips) < 1:
             raise ValueError("max_consecutive_skips must be >= 1, got %r" % (max_consecutive_skips,))
         self.max_consecutive_skips = int(max_consecutive_skips)
@@ -611,7 +630,11 @@ class Trainer:
                     followed = self.dynamics is not None and self.dynamics_every and (self.iterations + 1) % self.dynamics_every == 0
                     if followed:
                         self.dynamics.mark()          # one launch on this stream: the base this iteration's delta is taken from
-                    out = self._iteration()
+                    if self.formats is not None and self.formats_every and (self.iterations + 1) % self.formats_every == 0:
+                        with self.formats.iteration(self.iterations + 1):          # the tap is on for this iteration only
+                            out = self._iteration()
+                    else:
+                        out = self._iteration()
                     if self.average is not None:
                         self.average.update()          # one launch on this stream, behind the iteration's last write
                     self.i += 1
@@ -639,6 +662,9 @@ class Trainer:
             if self.dynamics is not None and self.dynamics_every:
                 self.written += self.dynamics.save(os.path.join(self.out, "error"), e + 1)
                 self.dynamics.clear()
+            if self.formats is not None and self.formats_every:
+                self.written += self.formats.save(os.path.join(self.out, "error"), e + 1)
+                self.formats.clear()
             if self._guards():
                 self.written.append(self._save_guards(e + 1))         # raises, before the save below, if a guard is exhausted
             if self.swd is not None:
@@ -683,6 +709,9 @@ def parser():
     ap.add_argument("--dynamics-every", type=int, default=0, metavar="N",
                     help="around every N-th iteration, record per-tensor update-to-weight ratios and per-layer spectral norms "
                          "(OUT/error/EPOCH-dynamics.npz); 0: off")
+    ap.add_argument("--formats-every", type=int, default=0, metavar="N",
+                    help="every N-th iteration, audit the operands of every dense contraction against fp8, MX and bf16 formats "
+                         "(OUT/error/EPOCH-formats.npz); eager runs only, not with --graph; 0: off")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
                     help="step both networks with GuardedNadam and scale the gradients down to the global L2 norm X where theirs is "
                          "larger (OUT/error/EPOCH-guard.json holds the counters); 0: guard without clipping")
@@ -725,6 +754,10 @@ def main(argv=None):
         ap.error("--stats-every must be >= 0")
     if args.dynamics_every < 0:
         ap.error("--dynamics-every must be >= 0")
+    if args.formats_every < 0:
+        ap.error("--formats-every must be >= 0")
+    if args.formats_every > 0 and args.graph:
+        ap.error("--formats-every audits eager iterations: a replayed graph runs no Python, so not with --graph")
     if args.clip_grad_norm is not None and not (0.0 <= args.clip_grad_norm < float("inf")):
         ap.error("--clip-grad-norm must be finite and >= 0")
     if args.max_consecutive_skips < 1:
@@ -792,6 +825,10 @@ def main(argv=None):
     if args.dynamics_every > 0:
         from .dynamics import RunDynamics
         dynamics = RunDynamics(gen, dis)
+    formats = None
+    if args.formats_every > 0:
+        from .formats import FormatAudit
+        formats = FormatAudit(gen, dis)
     snapshot = None
     if args.rollback_every > 0:
         from .snapshot import TrainingSnapshot
@@ -801,7 +838,7 @@ def main(argv=None):
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
                       dynamics=dynamics, dynamics_every=args.dynamics_every, neighbours=neighbours, manifold=manifold,
-                      sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
+                      formats=formats, formats_every=args.formats_every, sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
     else:
