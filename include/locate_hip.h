@@ -629,6 +629,30 @@ int locate_nn_within(const int8_t* qcodes, const int64_t* qnorms, const int32_t*
                      const int32_t* rflags, int N, int row_bytes, const int64_t* radius2, const int32_t* skip, int32_t* hits, int32_t* covered,
                      void* workspace, void* stream);
 
+/* ---- radial power spectrum of image planes (csrc/spectrum.hip; locate_amd/spectrum.py).  Per plane x fp32 [S, S], S in {32, 64,
+ *      128, 256}, H = S / 2, against the caller's tables cos_table / sin_table fp32 [S][S] (C[k][j] = cos(2 pi k j / S) w[j], Sn
+ *      likewise; 16-byte aligned): Ar[y][k] = sum_x x[y][x] C[k][x], Ai[y][k] = - sum_x x[y][x] Sn[k][x]; Yr[a][k] = sum_y C[a][y]
+ *      Ar[y][k] + Sn[a][y] Ai[y][k], Yi[a][k] = sum_y C[a][y] Ai[y][k] - Sn[a][y] Ar[y][k] for a = 0 .. S - 1, k = 0 .. H, every sum
+ *      in fp32 on v_mfma_f32_16x16x4_f32 (the summation order is the kernel's own); power[a][k] = ((double) Yr^2 + (double) Yi^2)
+ *      m[k] / S^4, m = 1 for k in {0, H} and 2 otherwise.  The radial bins arrive sorted: slot int32 [S][H + 1] is the place of
+ *      (a, k) in the list of all S (H + 1) frequencies ordered by (bin, a, k), start int32 [R + 1] the bins' first places
+ *      (start[R] = S (H + 1)); entries outside the list are clamped into it.  spectra float64 [planes][R]: spectra[p][r] = the sum
+ *      of the powers of bin r, four interleaved partial sums added as (p0 + p1) + (p2 + p3).  No atomics: the same words from call
+ *      to call, whatever else is in the call and whatever the alignment of x (4-byte; S >= 128: 16-byte).  A plane that holds a
+ *      NaN or an Inf gives a spectrum that is not finite.  S <= 64 is one launch and needs no workspace (it may be null); S >= 128
+ *      is three launches through `workspace`: locate_spectrum_workspace_bytes(planes, S) bytes, 16-byte aligned, need not be zeroed.
+ *      locate_spectrum_summary: spectra float64 [n][channels][R], count float64 [R] (a bin's multiplicity).  flags (`workspace`:
+ *      locate_spectrum_summary_workspace_bytes(n channels) bytes, 4-byte aligned) mark the planes whose spectrum is not finite; then
+ *      per (channel, bin), over the OTHER planes of the channel in ascending order (one fixed block sum): sums[0][c][r] = sum of
+ *      spectra / count, sums[1][c][r] = sum of its square (sums float64 [2][channels][R]); nonfinite int32 [channels] = the marked
+ *      planes of each channel.  Two launches, no atomics. ---- */
+size_t locate_spectrum_workspace_bytes(int planes, int S);
+int locate_spectrum_planes(const float* x, int planes, int S, const float* cos_table, const float* sin_table, const int32_t* slot,
+                           const int32_t* start, int R, double* spectra, void* workspace, void* stream);
+size_t locate_spectrum_summary_workspace_bytes(int planes);
+int locate_spectrum_summary(const double* spectra, int n, int channels, int R, const double* count, double* sums, int32_t* nonfinite,
+                            void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--swd-images 0] [--ema-half-life 0] [--stats-every 0] [--dynamics-every 0] [--formats-every 0]
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
                              [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0] [--neighbours 0] [--neighbours-k 3]
-                             [--manifold 0] [--manifold-k 3]
+                             [--manifold 0] [--manifold-k 3] [--spectrum-images 0] [--spectrum-window none]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -61,7 +61,11 @@ Differences from the reference, all additions:
   * `manifold=` / `--manifold IMAGES` (off by default): after every epoch precision, recall, density and coverage of IMAGES
     generated samples against IMAGES real images (`locate_amd.manifold`, `--manifold-k` neighbours per ball), exact in the 8-bit
     domain, with a real-against-real baseline: a record in `OUT/error/manifold.json`.  It tells lost modes from lost quality.  The
-    evaluation has no side effect on the training; under data parallelism only rank 0 evaluates."""
+    evaluation has no side effect on the training; under data parallelism only rank 0 evaluates;
+  * `spectrum=` / `--spectrum-images N` (off by default): after every epoch the radial power spectrum of N generated samples
+    against N real images (`locate_amd.spectrum`, `--spectrum-window hann` for a Hann window), with a real-against-real baseline:
+    a record in `OUT/error/spectrum.json`.  It shows the excess at high frequencies and the checkerboard that up-convolutions
+    leave.  The evaluation has no side effect on the training; under data parallelism only rank 0 evaluates."""
 import argparse
 import json
 import os
@@ -235,6 +239,13 @@ class Trainer:
     fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/manifold.json` (written to a
     .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record - without the
     baseline, which is the same - goes under "average".  The evaluation leaves weights, u / v and optimizer states untouched.
+    Under data parallelism only rank 0 should be given one.
+
+    spectrum: a `RadialSpectrum` whose reference is set, or None (the default: nothing below happens, and every file, record and
+    key is what it is without this argument).  After each epoch's manifold record, `spectrum.evaluate(gen)` runs on the metric's own
+    fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/spectrum.json` (written to a
+    .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record - without the
+    baseline, which is the same - goes under "average".  The evaluation leaves weights, u / v and optimizer states untouched.
     Under data parallelism only rank 0 should be given one."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
@@ -242,7 +253,7 @@ class Trainer:
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
                  max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None, manifold=None,
-                 formats=None, formats_every=0):
+                 formats=None, formats_every=0, spectrum=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -276,6 +287,7 @@ class Trainer:
         self.swd = swd
         self.neighbours = neighbours
         self.manifold = manifold
+        self.spectrum = spectrum
         self.average = average
         self._ema_sampler = None
         if int(stats_every) < 0:
@@ -603,6 +615,21 @@ class Trainer:
             records[-1]["average"] = {k: v for k, v in value.items() if k != "baseline"}
         return _write_json(path, records)
 
+    def _spectrum(self, e):
+        """One record of the radial power spectrum into out/error/spectrum.json (written to a .tmp and renamed), for the metric's
+        own fixed latents; returns the file written."""
+        value = self.spectrum.evaluate(self.gen)
+        path = os.path.join(self.out, "error", "spectrum.json")
+        records = []
+        if os.path.exists(path):
+            with open(path) as f:
+                records = json.load(f)
+        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
+        if self.average is not None:
+            value = self.spectrum.evaluate(self.average.generator)
+            records[-1]["average"] = {k: v for k, v in value.items() if k != "baseline"}
+        return _write_json(path, records)
+
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
         returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
@@ -673,6 +700,8 @@ class Trainer:
                 self.written += self._nearest(e)
             if self.manifold is not None:
                 self.written.append(self._manifold(e))
+            if self.spectrum is not None:
+                self.written.append(self._spectrum(e))
             self.epoch, self.sub = e + 1, 0
             if self.stats is not None:
                 self._check_stats(before_save=True)
@@ -736,6 +765,12 @@ def parser():
                     help="after every epoch, precision, recall, density and coverage of IMAGES generated samples against IMAGES real "
                          "images, exact in the 8-bit domain, with a real-against-real baseline (OUT/error/manifold.json); 0: off")
     ap.add_argument("--manifold-k", type=int, default=3, metavar="K", help="a ball reaches to the K-th nearest other image, 1 .. 8")
+    ap.add_argument("--spectrum-images", type=int, default=0, metavar="N",
+                    help="after every epoch, the radial power spectrum of N generated samples against N real images, with a "
+                         "real-against-real baseline (OUT/error/spectrum.json): the high-frequency excess and the checkerboard of "
+                         "up-convolutions; image sizes 32, 64, 128, 256; 0: off")
+    ap.add_argument("--spectrum-window", choices=("none", "hann"), default="none",
+                    help="window applied to both axes before the transform (none: what the cited papers do)")
     return ap
 
 
@@ -750,6 +785,10 @@ def main(argv=None):
         ap.error("--manifold must be >= 0")
     if not 1 <= args.manifold_k <= 8:
         ap.error("--manifold-k must be 1 .. 8")
+    if args.spectrum_images < 0:
+        ap.error("--spectrum-images must be >= 0")
+    if args.spectrum_images > 0 and args.image_size not in (32, 64, 128, 256):
+        ap.error("--spectrum-images takes --image-size 32, 64, 128 or 256")
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
     if args.dynamics_every < 0:
@@ -813,6 +852,12 @@ def main(argv=None):
         manifold = ManifoldMetrics(args.image_size, k=args.manifold_k, images=args.manifold, seed=args.seed, chunk=min(64, args.manifold),
                                    device=dev)
         manifold.reference_from_store(pipeline.store)
+    spectrum = None
+    if args.spectrum_images > 0:
+        from .spectrum import RadialSpectrum
+        spectrum = RadialSpectrum(args.image_size, images=args.spectrum_images, seed=args.seed, chunk=min(64, args.spectrum_images),
+                                  window=args.spectrum_window, device=dev)
+        spectrum.reference_from_pipeline(pipeline)
     average = None
     if args.ema_half_life > 0:
         from .average import AveragedGenerator
@@ -838,7 +883,7 @@ def main(argv=None):
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
                       dynamics=dynamics, dynamics_every=args.dynamics_every, neighbours=neighbours, manifold=manifold,
-                      formats=formats, formats_every=args.formats_every, sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
+                      formats=formats, formats_every=args.formats_every, spectrum=spectrum, sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
     else:
