@@ -653,6 +653,20 @@ size_t locate_spectrum_summary_workspace_bytes(int planes);
 int locate_spectrum_summary(const double* spectra, int n, int channels, int R, const double* count, double* sums, int32_t* nonfinite,
                             void* workspace, void* stream);
 
+/* ---- multi-scale SSIM of image pairs in the 8-bit domain (csrc/msssim.hip; locate_amd/msssim.py; the definition in float64 numpy:
+ *      tests/helpers/msssim_model.py).  Pair i is row i of `a` against row i of `b`: code rows as locate_nn_encode writes them (c, y, x
+ *      order, value = code + 128), 16-byte aligned, row_bytes >= 3 S^2 a multiple of 16; S in {32, 64, 128, 256}.  Five levels of side
+ *      S >> l, level l + 1 the 2 x 2 mean of level l (exact in fp32); per level the n = min(11, side) taps of row l of `taps` (float64
+ *      [5][11], zero padded), "valid", rows then columns, every product and sum in float64 in one fixed order.  out float64
+ *      [pairs][2][5]: the means over the three channels' outputs of ssim (out[i][0][l]) and cs (out[i][1][l]).  The flags (int32
+ *      [pairs], locate_nn_encode's) may be null; a pair with a flagged member gets ten NaNs.  No atomics: a pair's ten numbers depend
+ *      on its two rows alone, (a, b) gives the bits of (b, a), and a row against itself 1.0 ten times.  S <= 64 is one launch and needs
+ *      no workspace (it may be null); 128 is two launches, 256 three, through `workspace`: locate_msssim_workspace_bytes(pairs, S)
+ *      bytes, 16-byte aligned, need not be zeroed, and at most 65535 pairs a call. ---- */
+size_t locate_msssim_workspace_bytes(int pairs, int S);
+int locate_msssim_pairs(const int8_t* a, const int32_t* aflags, const int8_t* b, const int32_t* bflags, int pairs, int row_bytes, int S,
+                        const double* taps, double* out, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

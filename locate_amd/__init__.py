@@ -21,6 +21,7 @@ from .stats import NonFiniteError, RunStatistics, tensor_statistics  # noqa: F40
 from .dynamics import RunDynamics, tensor_deltas  # noqa: F401
 from .formats import FormatAudit, format_errors  # noqa: F401
 from .spectrum import RadialSpectrum, dft_tables, radial_bins, radial_spectrum, spectrum_summary  # noqa: F401
+from .msssim import MultiScaleSSIM, ms_ssim, ms_ssim_levels, ms_ssim_value, window_taps  # noqa: F401
 from .guard import GuardedNadam, GuardExhausted  # noqa: F401
 from .snapshot import NoSnapshot, StateSnapshot, TrainingSnapshot, arena_layout  # noqa: F401
 from .spill import (SnapshotSpill, SpillCorrupt, SpillMismatch, digest_model, read_spill, restore_training_state,  # noqa: F401

@@ -178,6 +178,8 @@ PROTOTYPES = {
     "locate_spectrum_planes": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p]),
     "locate_spectrum_summary_workspace_bytes": (c_sz, [c_i]),
     "locate_spectrum_summary": (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "locate_msssim_workspace_bytes": (c_sz, [c_i, c_i]),
+    "locate_msssim_pairs": (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
     "locate_nn_row_bytes": (c_i, [c_i]),
     "locate_nn_encode": (c_i, [c_p, c_i, c_i, c_p, c_p, c_p, c_p]),
     "locate_nn_search_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
@@ -193,7 +195,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 18
+EXPECTED_ABI = 19
 
 
 _lib = None

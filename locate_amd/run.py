@@ -8,6 +8,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
                              [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0] [--neighbours 0] [--neighbours-k 3]
                              [--manifold 0] [--manifold-k 3] [--spectrum-images 0] [--spectrum-window none]
+                             [--msssim-pairs 0]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -65,7 +66,11 @@ Differences from the reference, all additions:
   * `spectrum=` / `--spectrum-images N` (off by default): after every epoch the radial power spectrum of N generated samples
     against N real images (`locate_amd.spectrum`, `--spectrum-window hann` for a Hann window), with a real-against-real baseline:
     a record in `OUT/error/spectrum.json`.  It shows the excess at high frequencies and the checkerboard that up-convolutions
-    leave.  The evaluation has no side effect on the training; under data parallelism only rank 0 evaluates."""
+    leave.  The evaluation has no side effect on the training; under data parallelism only rank 0 evaluates;
+  * `msssim=` / `--msssim-pairs N` (off by default): after every epoch the multi-scale SSIM between N pairs of generated samples
+    (`locate_amd.msssim`) beside that of N pairs of real images: a record in `OUT/error/msssim.json`.  It says how alike the samples
+    are, scale by scale; with `--ema-half-life` also how alike the live and the averaged generator's images of the same latents are.
+    The evaluation has no side effect on the training; under data parallelism only rank 0 evaluates."""
 import argparse
 import json
 import os
@@ -246,14 +251,22 @@ class Trainer:
     fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/spectrum.json` (written to a
     .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record - without the
     baseline, which is the same - goes under "average".  The evaluation leaves weights, u / v and optimizer states untouched.
-    Under data parallelism only rank 0 should be given one."""
+    Under data parallelism only rank 0 should be given one.
+
+    msssim: a `MultiScaleSSIM` (with its "real" reference, if wanted), or None (the default: nothing below happens, and every file,
+    record and key is what it is without this argument).  After each epoch's spectrum record, `msssim.evaluate(gen)` runs on the
+    metric's own fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/msssim.json`
+    (written to a .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record -
+    without "real", which is the same - goes under "average", and `msssim.evaluate_against(gen, average.generator)`, the two
+    generators' images of the same latents against each other, under "average_to_live".  The evaluation leaves weights, u / v and
+    optimizer states untouched.  Under data parallelism only rank 0 should be given one."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
                  max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None, manifold=None,
-                 formats=None, formats_every=0, spectrum=None):
+                 formats=None, formats_every=0, spectrum=None, msssim=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -288,6 +301,7 @@ class Trainer:
         self.neighbours = neighbours
         self.manifold = manifold
         self.spectrum = spectrum
+        self.msssim = msssim
         self.average = average
         self._ema_sampler = None
         if int(stats_every) < 0:
@@ -630,6 +644,22 @@ class Trainer:
             records[-1]["average"] = {k: v for k, v in value.items() if k != "baseline"}
         return _write_json(path, records)
 
+    def _msssim(self, e):
+        """One record of the multi-scale SSIM into out/error/msssim.json (written to a .tmp and renamed), for the metric's own fixed
+        latents; returns the file written."""
+        value = self.msssim.evaluate(self.gen)
+        path = os.path.join(self.out, "error", "msssim.json")
+        records = []
+        if os.path.exists(path):
+            with open(path) as f:
+                records = json.load(f)
+        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
+        if self.average is not None:
+            value = self.msssim.evaluate(self.average.generator)
+            records[-1]["average"] = {k: v for k, v in value.items() if k != "real"}
+            records[-1]["average_to_live"] = self.msssim.evaluate_against(self.gen, self.average.generator)
+        return _write_json(path, records)
+
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
         returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
@@ -702,6 +732,8 @@ class Trainer:
                 self.written.append(self._manifold(e))
             if self.spectrum is not None:
                 self.written.append(self._spectrum(e))
+            if self.msssim is not None:
+                self.written.append(self._msssim(e))
             self.epoch, self.sub = e + 1, 0
             if self.stats is not None:
                 self._check_stats(before_save=True)
@@ -771,6 +803,9 @@ def parser():
                          "up-convolutions; image sizes 32, 64, 128, 256; 0: off")
     ap.add_argument("--spectrum-window", choices=("none", "hann"), default="none",
                     help="window applied to both axes before the transform (none: what the cited papers do)")
+    ap.add_argument("--msssim-pairs", type=int, default=0, metavar="N",
+                    help="after every epoch, the multi-scale SSIM between N pairs of generated samples beside that of N pairs of real "
+                         "images (OUT/error/msssim.json): how alike the samples are, scale by scale; image sizes 32, 64, 128, 256; 0: off")
     return ap
 
 
@@ -789,6 +824,10 @@ def main(argv=None):
         ap.error("--spectrum-images must be >= 0")
     if args.spectrum_images > 0 and args.image_size not in (32, 64, 128, 256):
         ap.error("--spectrum-images takes --image-size 32, 64, 128 or 256")
+    if args.msssim_pairs < 0:
+        ap.error("--msssim-pairs must be >= 0")
+    if args.msssim_pairs > 0 and args.image_size not in (32, 64, 128, 256):
+        ap.error("--msssim-pairs takes --image-size 32, 64, 128 or 256")
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
     if args.dynamics_every < 0:
@@ -858,6 +897,11 @@ def main(argv=None):
         spectrum = RadialSpectrum(args.image_size, images=args.spectrum_images, seed=args.seed, chunk=min(64, args.spectrum_images),
                                   window=args.spectrum_window, device=dev)
         spectrum.reference_from_pipeline(pipeline)
+    msssim = None
+    if args.msssim_pairs > 0:
+        from .msssim import MultiScaleSSIM
+        msssim = MultiScaleSSIM(args.image_size, pairs=args.msssim_pairs, seed=args.seed, chunk=min(64, 2 * args.msssim_pairs) // 2 * 2, device=dev)
+        msssim.reference_from_pipeline(pipeline)
     average = None
     if args.ema_half_life > 0:
         from .average import AveragedGenerator
@@ -883,7 +927,7 @@ def main(argv=None):
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
                       dynamics=dynamics, dynamics_every=args.dynamics_every, neighbours=neighbours, manifold=manifold,
-                      formats=formats, formats_every=args.formats_every, spectrum=spectrum, sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
+                      formats=formats, formats_every=args.formats_every, spectrum=spectrum, msssim=msssim, sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
     else:
