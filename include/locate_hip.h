@@ -86,6 +86,13 @@ size_t locate_norm_bwd_fused_plane_offset(void);
 int locate_norm_bwd_fused(const float* x, const float* g, const float* stats, const float* scale, int scale_per_sample,
                           const float* bias, int with_act, float* dx, float* dscale_sample, int B, int C, int hw, int groups,
                           void* workspace, int accumulate_dx, void* stream);
+/* the plane pass of locate_norm_bwd_fused alone (S1 / S2, dscale_sample and the per-block group sums as that call leaves them):
+ * dx is formed by the kernel that consumes it, locate_gate_bwd_term, from the first locate_norm_bwd_fused_partials(B, C) block
+ * records at the start of `workspace` */
+int locate_norm_bwd_fused_partials(int B, int C);
+int locate_norm_bwd_planes(const float* x, const float* g, const float* stats, const float* scale, int scale_per_sample,
+                           const float* bias, int with_act, float* dscale_sample, int B, int C, int hw, int groups,
+                           void* workspace, void* stream);
 int locate_fin_norm_channels(const void* records, int n, void* stream);
 size_t locate_channel_sum_workspace_bytes(int B, int C, int hw);
 int locate_channel_sum(const float* g, float* out, int B, int C, int hw, int64_t batch_stride, void* workspace, void* stream);
@@ -106,6 +113,29 @@ int locate_gate_bwd_partials(int64_t planes, int hw);
 int locate_gate_bwd(const float* x, const float* a, int a_per_plane, const float* gamma, const float* g, float* dx, float* da,
                     float* dgamma, int64_t planes, int hw, void* workspace, int accumulate_dx,
                     void* da_absmax /* nullable: largest |da| (full-map form), see locate_roottanh_bwd */, void* stream);
+/* The same backward with the gradient w.r.t. the gate's output FORMED inside the kernel instead of read from g - the gate's
+ * output out = (gamma a + 1) x is recomputed bit for bit, so the element-wise launch that would have produced g, and its pass
+ * over the tensor, go away.  Same results, bit for bit, as the two calls it replaces.
+ *   LOCATE_GATE_TERM_NONE      locate_gate_bwd
+ *   LOCATE_GATE_TERM_NORM      out fed an InPlaceNorm whose backward ran its plane pass only (locate_norm_bwd_planes with the
+ *                              same B, C, hw, groups; B * C == planes): the gradient is that norm's dx from go, stats, scale,
+ *                              bias and the first npartial = locate_norm_bwd_fused_partials(B, C) records of its workspace
+ *                              (`partial`), plus g where has_share says that another consumer of out left its share there
+ *                              (dx + share, locate_norm_bwd_fused's accumulate order); g is not read otherwise
+ *   LOCATE_GATE_TERM_ROOTTANH  out fed a RootTanh: the gradient is RootTanh'(out) g (locate_roottanh_bwd) */
+enum { LOCATE_GATE_TERM_NONE = 0, LOCATE_GATE_TERM_NORM = 1, LOCATE_GATE_TERM_ROOTTANH = 2 };
+typedef struct {
+    int32_t kind, with_act, per_sample, has_share;
+    const float* go;
+    const float* stats;
+    const float* scale;
+    const float* bias;
+    const double* partial;
+    int32_t npartial, B, C, groups;
+} LocateGateTerm;
+int locate_gate_bwd_term(const float* x, const float* a, int a_per_plane, const float* gamma, const float* g, float* dx, float* da,
+                         float* dgamma, int64_t planes, int hw, void* workspace, int accumulate_dx, void* da_absmax,
+                         LocateGateTerm term, void* stream);
 
 /* ---- softmax over the last dimension of [rows, n] (libs/attention.py:35,47) ---- */
 int locate_softmax_fwd(const float* x, float* y, int64_t rows, int n, void* stream);

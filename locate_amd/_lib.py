@@ -22,6 +22,16 @@ c_d = ctypes.c_double
 c_sz = ctypes.c_size_t
 c_ip = ctypes.POINTER(ctypes.c_int)
 
+
+class GateTerm(ctypes.Structure):
+    """LocateGateTerm of include/locate_hip.h (passed by value to locate_gate_bwd_term): how the gradient w.r.t. a gate's output
+    is formed inside the gate's backward kernel."""
+    NONE, NORM, ROOTTANH = 0, 1, 2
+    _fields_ = [("kind", ctypes.c_int32), ("with_act", ctypes.c_int32), ("per_sample", ctypes.c_int32), ("has_share", ctypes.c_int32),
+                ("go", c_p), ("stats", c_p), ("scale", c_p), ("bias", c_p), ("partial", c_p),
+                ("npartial", ctypes.c_int32), ("B", ctypes.c_int32), ("C", ctypes.c_int32), ("groups", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/locate_hip.h one to one
 PROTOTYPES = {
     "locate_last_error": (ctypes.c_char_p, []),
@@ -48,6 +58,8 @@ PROTOTYPES = {
     "locate_norm_bwd_fused_workspace_bytes": (c_sz, [c_i, c_i]),
     "locate_norm_bwd_fused_plane_offset": (c_sz, []),
     "locate_norm_bwd_fused": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
+    "locate_norm_bwd_fused_partials": (c_i, [c_i, c_i]),
+    "locate_norm_bwd_planes": (c_i, [c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     "locate_fin_norm_channels": (c_i, [c_p, c_i, c_p]),
     "locate_channel_sum_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "locate_channel_sum": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i64, c_p, c_p]),
@@ -55,6 +67,7 @@ PROTOTYPES = {
     "locate_gate_fwd_stats": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i64, c_i, c_i, c_p, c_p]),
     "locate_gate_bwd_workspace_bytes": (c_sz, [c_i64]),
     "locate_gate_bwd": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_i, c_p, c_p]),
+    "locate_gate_bwd_term": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i64, c_i, c_p, c_i, c_p, GateTerm, c_p]),
     "locate_softmax_fwd": (c_i, [c_p, c_p, c_i64, c_i, c_p]),
     "locate_softmax_bwd": (c_i, [c_p, c_p, c_p, c_i64, c_i, c_p]),
     "locate_upsample2x_fwd": (c_i, [c_p, c_p, c_i64, c_i, c_i, c_p]),
@@ -195,7 +208,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 19
+EXPECTED_ABI = 20
 
 
 _lib = None

@@ -4,6 +4,7 @@
 //   residual gate fwd/bwd   reference libs/merge.py:19-39 (incl. the x^2 gamma-gradient as coded)
 //   channel-slice copy      reference libs/merge.py:15 (torch.cat along channels) and its backward
 #include "common.h"
+#include "normterm.h"          // LocateGateTerm, norm_dx: the gate backward's incoming-gradient terms
 
 // ---------------------------------------------------------------------------------------------
 // RootTanh:  y = (x^2+1)^(1/4) * tanh(x)
@@ -332,19 +333,89 @@ __device__ __noinline__ float gate_plane_da_nonfinite(const float* __restrict__ 
 }
 __device__ __forceinline__ bool gate_gamma_finite(float gm) { return fabsf(gm) <= 3.402823466e38f; }
 
+// ---- incoming-gradient terms (locate_gate_bwd_term) ----
+// Every block output is a gate output out = (gamma a + 1) x that feeds the next gate as its skip input and an InPlaceNorm as the
+// branch input.  The norm's backward would add its dx into the buffer the skip consumer wrote (norm_bwd_dx_kernel: a read of out,
+// go and the buffer, a write of the sum), only for this kernel to read the sum back.  With a term the gate backward forms
+//     g = norm_dx(out, go) (+ the other consumer's share)
+// itself: out is recomputed from x, a and gamma - the forward's bits, a pinned product (mul_pinned) - and dx is norm_dx of normterm.h, the
+// dx kernel's own code with the dx kernel's addition order (o + share).  GATE_TERM_ROOTTANH is the output head's
+// g = RootTanh'(out) g_in (unary_bwd_kernel<0>).  GATE_TERM_NONE: g is read from memory, the code below is not instantiated.
+constexpr bool gate_term_is_norm(int term) { return term == GATE_TERM_NORM || term == GATE_TERM_NORM_ACT; }
+
+struct GateTermPlane { float mu, inv_s, y, b, k, m; };          // what norm_dx needs of ONE plane of `out`
+
+// p: the plane of the norm's [B, C, hw] view (group p / planes_g, channel p % C, per-sample scale[p])
+template <int TERM>
+__device__ __forceinline__ GateTermPlane gate_term_plane(const LocateGateTerm& t, const float (*tc)[2], unsigned p, unsigned planes_g) {
+    GateTermPlane tp = {0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (gate_term_is_norm(TERM)) {
+        const unsigned grp = p / planes_g, c = p % (unsigned)t.C;
+        tp.mu = t.stats[2 * grp];
+        tp.inv_s = 1.0f / t.stats[2 * grp + 1];
+        tp.y = t.scale[t.per_sample ? p : c];
+        tp.b = TERM == GATE_TERM_NORM_ACT ? t.bias[c] : 0.0f;
+        tp.m = tc[grp][0];
+        tp.k = tc[grp][1];
+    }
+    return tp;
+}
+
+// g * (gamma a + 1) with g as the instruction's FIRST operand.  Under a NaN gamma both factors are NaNs (of either sign: the
+// norm's dx negates its mean term) and the multiplier returns the first one it meets; the kernels that read g from memory
+// multiply in this order, and the folded forms are held to their bits - NaN words included (tests/test_gpu_gate_fold.py).
+__device__ __forceinline__ float gate_mul_g_first(float g, float m) {
+    float r;
+    asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(g), "v"(m));
+    return r;
+}
+
+template <int TERM>
+__device__ __forceinline__ float gate_term_g(const GateTermPlane& tp, float out, float gin, float share, int has_share) {
+    if constexpr (TERM == GATE_TERM_ROOTTANH) return roottanh_grad_f(out, gin);
+    const float o = norm_dx<TERM == GATE_TERM_NORM_ACT>(out, gin, tp.mu, tp.inv_s, tp.y, tp.b, tp.k, tp.m);
+    return has_share ? o + share : o;
+}
+
+// {m, k} of every group a block may meet (stacked passes: <= NORM_MAX_GROUPS), wave w takes group w - norm_bwd_dx_kernel's sums
+template <int TERM>
+__device__ __forceinline__ void gate_term_consts(const LocateGateTerm& t, int64_t n_group, float (*tc)[2]) {
+    if constexpr (gate_term_is_norm(TERM)) {
+        const int wid = threadIdx.x >> 6;
+        if (wid < t.groups) norm_group_consts(t.partial, t.npartial, wid, t.stats[2 * wid + 1], n_group, (int)(threadIdx.x & 63), tc[wid]);
+        __syncthreads();
+    }
+}
+
+// gate_plane_da_nonfinite with g formed by the term (one value of a per plane: ap)
+template <int TERM>
+__device__ __noinline__ float gate_plane_da_nonfinite_term(const float* __restrict__ x, const float* __restrict__ gs,
+                                                           const float* __restrict__ share, int hw, float gm, float ap,
+                                                           GateTermPlane tp, int has_share) {
+    float s = 0.0f;
+    const float mv = fmaf(gm, ap, 1.0f);
+    for (int i = 0; i < hw; ++i) {
+        const float g = gate_term_g<TERM>(tp, mul_pinned(mv, x[i]), gs[i], has_share ? share[i] : 0.0f, has_share);
+        s += (x[i] * g) * gm;
+    }
+    return s;
+}
+
 // dx, da (full, or gamma * sum x*g per plane in broadcast mode) and, per BLOCK, the sum of x^2*g over the planes the
 // block visited (fixed order: deterministic).  WPP waves share a plane: 1 for small planes (one wave per plane),
 // 4 (the whole block) for planes of >= 1024 elements, 16-byte accesses when hw % 4 == 0.
-template <int WPP>
+// ELEM (norm terms): a 1x1 map re-read as planes of 64 (locate_gate_bwd_term) - the norm's plane is the ELEMENT index
+template <int WPP, int TERM, bool ELEM = false>
 __global__ void __launch_bounds__(256) gate_bwd_plane_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                              const float* __restrict__ gamma, const float* __restrict__ g,
                                                              float* __restrict__ dx, float* __restrict__ da_full,
                                                              float* __restrict__ da_plane, double* __restrict__ block_x2g,
                                                              int64_t planes, int hw, int a_per_plane, int accumulate_dx,
-                                                             unsigned* __restrict__ da_absmax) {
+                                                             unsigned* __restrict__ da_absmax, const LocateGateTerm t) {
     __shared__ double wsum[4], px2g[4];
     __shared__ float pxg[4];
     __shared__ float amax_scratch[16];
+    __shared__ float tc[NORM_MAX_GROUPS][2];          // (terms only) {m, k} of the norm's groups
     float am = 0.0f;                    // largest |da| (full-map form): the branch's last conv consumes da in its fp16-piece form
     double wacc = 0.0;
     const float gm = gamma[0];
@@ -353,20 +424,50 @@ __global__ void __launch_bounds__(256) gate_bwd_plane_kernel(const float* __rest
     const int nsub = WPP == 1 ? 64 : 256;
     const int64_t first = WPP == 1 ? (((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6) : (int64_t)blockIdx.x;
     const int64_t step = WPP == 1 ? (((int64_t)gridDim.x * blockDim.x) >> 6) : (int64_t)gridDim.x;
-    const bool vec = (hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx) |
-                                        (a_per_plane ? 0 : (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(da_full)))) & 15) == 0;
+    // with a norm term: where the norm's gradient go is read (g is then the other consumer's share); otherwise g itself
+    const float* __restrict__ gs = gate_term_is_norm(TERM) ? t.go : g;
+    constexpr bool elem = ELEM;
+    const unsigned planes_g = gate_term_is_norm(TERM) ? (unsigned)((int64_t)t.B * t.C / t.groups) : 1u;
+    const int has_share = gate_term_is_norm(TERM) ? t.has_share : 0;
+    if constexpr (gate_term_is_norm(TERM)) gate_term_consts<TERM>(t, (int64_t)planes_g * (elem ? 1 : hw), tc);
+    bool vec = (hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx) |
+                                  (a_per_plane ? 0 : (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(da_full)))) & 15) == 0;
+    if constexpr (gate_term_is_norm(TERM)) vec = vec && (reinterpret_cast<uintptr_t>(gs) & 15) == 0;
     for (int64_t p = first; p < planes; p += step) {
         const int64_t base = p * hw;
         const float ap = a_per_plane ? a[p] : 0.0f;
         float sxg = 0.0f, sx2g = 0.0f;
+        GateTermPlane tp = {0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (gate_term_is_norm(TERM))
+            if (!elem) tp = gate_term_plane<TERM>(t, tc, (unsigned)p, planes_g);
         if (vec) {
             for (int i = sub; i < (hw >> 2); i += nsub) {
-                const float4 xv = reinterpret_cast<const float4*>(x + base)[i], gv = reinterpret_cast<const float4*>(g + base)[i];
+                const float4 xv = reinterpret_cast<const float4*>(x + base)[i];
+                float4 gv = reinterpret_cast<const float4*>(gs + base)[i];
                 float4 av = make_float4(ap, ap, ap, ap);
                 if (!a_per_plane) av = reinterpret_cast<const float4*>(a + base)[i];
+                if constexpr (TERM != GATE_TERM_NONE) {
+                    const float4 ov = make_float4(mul_pinned(fmaf(gm, av.x, 1.0f), xv.x), mul_pinned(fmaf(gm, av.y, 1.0f), xv.y),
+                                                  mul_pinned(fmaf(gm, av.z, 1.0f), xv.z), mul_pinned(fmaf(gm, av.w, 1.0f), xv.w));
+                    float4 sh = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (has_share) sh = reinterpret_cast<const float4*>(g + base)[i];
+                    if (elem) {
+                        const unsigned e = (unsigned)(base + 4 * i);
+                        gv.x = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e, planes_g), ov.x, gv.x, sh.x, has_share);
+                        gv.y = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e + 1, planes_g), ov.y, gv.y, sh.y, has_share);
+                        gv.z = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e + 2, planes_g), ov.z, gv.z, sh.z, has_share);
+                        gv.w = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e + 3, planes_g), ov.w, gv.w, sh.w, has_share);
+                    } else {
+                        gv.x = gate_term_g<TERM>(tp, ov.x, gv.x, sh.x, has_share); gv.y = gate_term_g<TERM>(tp, ov.y, gv.y, sh.y, has_share);
+                        gv.z = gate_term_g<TERM>(tp, ov.z, gv.z, sh.z, has_share); gv.w = gate_term_g<TERM>(tp, ov.w, gv.w, sh.w, has_share);
+                    }
+                }
                 const float4 xg = make_float4(xv.x * gv.x, xv.y * gv.y, xv.z * gv.z, xv.w * gv.w);
                 float4 o = make_float4(fmaf(gm, av.x, 1.0f) * gv.x, fmaf(gm, av.y, 1.0f) * gv.y, fmaf(gm, av.z, 1.0f) * gv.z,
                                        fmaf(gm, av.w, 1.0f) * gv.w);
+                if constexpr (TERM != GATE_TERM_NONE)
+                    o = make_float4(gate_mul_g_first(gv.x, fmaf(gm, av.x, 1.0f)), gate_mul_g_first(gv.y, fmaf(gm, av.y, 1.0f)),
+                                    gate_mul_g_first(gv.z, fmaf(gm, av.z, 1.0f)), gate_mul_g_first(gv.w, fmaf(gm, av.w, 1.0f)));
                 if (accumulate_dx) {
                     const float4 old = reinterpret_cast<const float4*>(dx + base)[i];
                     o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
@@ -382,10 +483,16 @@ __global__ void __launch_bounds__(256) gate_bwd_plane_kernel(const float* __rest
             }
         } else {
             for (int i = sub; i < hw; i += nsub) {
-                const float xv = x[base + i], gv = g[base + i];
+                const float xv = x[base + i];
+                float gv = gs[base + i];
                 const float av = a_per_plane ? ap : a[base + i];
+                if constexpr (TERM != GATE_TERM_NONE) {
+                    if (elem) tp = gate_term_plane<TERM>(t, tc, (unsigned)(base + i), planes_g);
+                    gv = gate_term_g<TERM>(tp, mul_pinned(fmaf(gm, av, 1.0f), xv), gv, has_share ? g[base + i] : 0.0f, has_share);
+                }
                 const float xg = xv * gv;
-                const float o = fmaf(gm, av, 1.0f) * gv;
+                float o = fmaf(gm, av, 1.0f) * gv;
+                if constexpr (TERM != GATE_TERM_NONE) o = gate_mul_g_first(gv, fmaf(gm, av, 1.0f));
                 dx[base + i] = accumulate_dx ? dx[base + i] + o : o;
                 if (!a_per_plane) { da_full[base + i] = xg * gm; am = fmaxf(am, fabsf(xg * gm)); }
                 sxg += xg;
@@ -396,16 +503,22 @@ __global__ void __launch_bounds__(256) gate_bwd_plane_kernel(const float* __rest
         const double s2 = wave_sum_d((double)sx2g);      // dgamma sums x^2 g with heavy cancellation: leave fp32 early
         if (WPP == 1) {
             wacc += s2;
-            if (lane == 0 && a_per_plane) da_plane[p] = gate_gamma_finite(gm) ? gm * sxg : gate_plane_da_nonfinite(x + base, g + base, hw, gm);
+            if (lane == 0 && a_per_plane) {
+                if (gate_gamma_finite(gm)) da_plane[p] = gm * sxg;
+                else if constexpr (TERM == GATE_TERM_NONE) da_plane[p] = gate_plane_da_nonfinite(x + base, g + base, hw, gm);
+                else da_plane[p] = gate_plane_da_nonfinite_term<TERM>(x + base, gs + base, g + base, hw, gm, ap, tp, has_share);
+            }
         } else {
             __syncthreads();
             if (lane == 0) { pxg[wid] = sxg; px2g[wid] = s2; }
             __syncthreads();
             if (threadIdx.x == 0) {
                 wacc += (px2g[0] + px2g[1]) + (px2g[2] + px2g[3]);
-                if (a_per_plane)
-                    da_plane[p] = gate_gamma_finite(gm) ? gm * ((pxg[0] + pxg[1]) + (pxg[2] + pxg[3]))
-                                                        : gate_plane_da_nonfinite(x + base, g + base, hw, gm);
+                if (a_per_plane) {
+                    if (gate_gamma_finite(gm)) da_plane[p] = gm * ((pxg[0] + pxg[1]) + (pxg[2] + pxg[3]));
+                    else if constexpr (TERM == GATE_TERM_NONE) da_plane[p] = gate_plane_da_nonfinite(x + base, g + base, hw, gm);
+                    else da_plane[p] = gate_plane_da_nonfinite_term<TERM>(x + base, gs + base, g + base, hw, gm, ap, tp, has_share);
+                }
             }
         }
     }
@@ -424,15 +537,16 @@ __global__ void __launch_bounds__(256) gate_bwd_plane_kernel(const float* __rest
 // wave per 4-element plane one lane worked, every plane paid two full wave reductions (the double one: 12 shuffles of 8 bytes) and
 // a wave walked ~50 planes one after the other: 25 - 70 us for tensors of a few hundred KB.  Per-plane sums: the same additions
 // in the same order as gate_bwd_plane_kernel<1> (whose idle lanes add exact zeros), hence the same bits.
-template <int LP>
+template <int LP, int TERM, bool ELEM = false>
 __global__ void __launch_bounds__(256) gate_bwd_small_kernel(const float* __restrict__ x, const float* __restrict__ a,
                                                              const float* __restrict__ gamma, const float* __restrict__ g,
                                                              float* __restrict__ dx, float* __restrict__ da_full,
                                                              float* __restrict__ da_plane, double* __restrict__ block_x2g,
                                                              int64_t planes, int hw, int a_per_plane, int accumulate_dx,
-                                                             unsigned* __restrict__ da_absmax) {
+                                                             unsigned* __restrict__ da_absmax, const LocateGateTerm t) {
     __shared__ double wsum[4];
     __shared__ float amax_scratch[16];
+    __shared__ float tc[NORM_MAX_GROUPS][2];          // (terms only) {m, k} of the norm's groups
     constexpr int PW = 64 / LP;
     float am = 0.0f;
     double wacc = 0.0;
@@ -442,19 +556,48 @@ __global__ void __launch_bounds__(256) gate_bwd_small_kernel(const float* __rest
     const int q4 = hw >> 2;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    // (see gate_bwd_plane_kernel)
+    const float* __restrict__ gs = gate_term_is_norm(TERM) ? t.go : g;
+    constexpr bool elem = ELEM;
+    const unsigned planes_g = gate_term_is_norm(TERM) ? (unsigned)((int64_t)t.B * t.C / t.groups) : 1u;
+    const int has_share = gate_term_is_norm(TERM) ? t.has_share : 0;
+    if constexpr (gate_term_is_norm(TERM)) gate_term_consts<TERM>(t, (int64_t)planes_g * (elem ? 1 : hw), tc);
     for (int64_t p0 = wave * PW; p0 < planes; p0 += nwaves * PW) {
         const int64_t p = p0 + gid;
         const bool live = p < planes;
         float sxg = 0.0f, sx2g = 0.0f;
+        float ap = 0.0f;
+        GateTermPlane tp = {0.0f, 1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         if (live && li < q4) {
             const int64_t base = p * hw;
-            const float ap = a_per_plane ? a[p] : 0.0f;
-            const float4 xv = reinterpret_cast<const float4*>(x + base)[li], gv = reinterpret_cast<const float4*>(g + base)[li];
+            ap = a_per_plane ? a[p] : 0.0f;
+            const float4 xv = reinterpret_cast<const float4*>(x + base)[li];
+            float4 gv = reinterpret_cast<const float4*>(gs + base)[li];
             float4 av = make_float4(ap, ap, ap, ap);
             if (!a_per_plane) av = reinterpret_cast<const float4*>(a + base)[li];
+            if constexpr (TERM != GATE_TERM_NONE) {
+                const float4 ov = make_float4(mul_pinned(fmaf(gm, av.x, 1.0f), xv.x), mul_pinned(fmaf(gm, av.y, 1.0f), xv.y),
+                                              mul_pinned(fmaf(gm, av.z, 1.0f), xv.z), mul_pinned(fmaf(gm, av.w, 1.0f), xv.w));
+                float4 sh = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (has_share) sh = reinterpret_cast<const float4*>(g + base)[li];
+                if (elem) {
+                    const unsigned e = (unsigned)(base + 4 * li);
+                    gv.x = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e, planes_g), ov.x, gv.x, sh.x, has_share);
+                    gv.y = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e + 1, planes_g), ov.y, gv.y, sh.y, has_share);
+                    gv.z = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e + 2, planes_g), ov.z, gv.z, sh.z, has_share);
+                    gv.w = gate_term_g<TERM>(gate_term_plane<TERM>(t, tc, e + 3, planes_g), ov.w, gv.w, sh.w, has_share);
+                } else {
+                    tp = gate_term_plane<TERM>(t, tc, (unsigned)p, planes_g);
+                    gv.x = gate_term_g<TERM>(tp, ov.x, gv.x, sh.x, has_share); gv.y = gate_term_g<TERM>(tp, ov.y, gv.y, sh.y, has_share);
+                    gv.z = gate_term_g<TERM>(tp, ov.z, gv.z, sh.z, has_share); gv.w = gate_term_g<TERM>(tp, ov.w, gv.w, sh.w, has_share);
+                }
+            }
             const float4 xg = make_float4(xv.x * gv.x, xv.y * gv.y, xv.z * gv.z, xv.w * gv.w);
             float4 o = make_float4(fmaf(gm, av.x, 1.0f) * gv.x, fmaf(gm, av.y, 1.0f) * gv.y, fmaf(gm, av.z, 1.0f) * gv.z,
                                    fmaf(gm, av.w, 1.0f) * gv.w);
+            if constexpr (TERM != GATE_TERM_NONE)
+                o = make_float4(gate_mul_g_first(gv.x, fmaf(gm, av.x, 1.0f)), gate_mul_g_first(gv.y, fmaf(gm, av.y, 1.0f)),
+                                gate_mul_g_first(gv.z, fmaf(gm, av.z, 1.0f)), gate_mul_g_first(gv.w, fmaf(gm, av.w, 1.0f)));
             if (accumulate_dx) {
                 const float4 old = reinterpret_cast<const float4*>(dx + base)[li];
                 o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w;
@@ -476,7 +619,11 @@ __global__ void __launch_bounds__(256) gate_bwd_small_kernel(const float* __rest
         }
         if (live && li == 0) {
             wacc += s2;
-            if (a_per_plane) da_plane[p] = gate_gamma_finite(gm) ? gm * sxg : gate_plane_da_nonfinite(x + p * hw, g + p * hw, hw, gm);
+            if (a_per_plane) {
+                if (gate_gamma_finite(gm)) da_plane[p] = gm * sxg;
+                else if constexpr (TERM == GATE_TERM_NONE) da_plane[p] = gate_plane_da_nonfinite(x + p * hw, g + p * hw, hw, gm);
+                else da_plane[p] = gate_plane_da_nonfinite_term<TERM>(x + p * hw, gs + p * hw, g + p * hw, hw, gm, ap, tp, has_share);
+            }
         }
     }
     wacc = wave_sum_d(wacc);          // the plane leaders' sums (other lanes hold 0), fixed order
@@ -533,24 +680,28 @@ LOCATE_API int locate_gate_bwd_partials(int64_t planes, int hw) { return (int)ga
 // da: [planes*hw] when a_per_plane == 0, [planes] otherwise.  dgamma: one float (overwritten).
 // (Tried and dropped: the kernel's last-arriving block reducing dgamma itself instead of the second launch - up to 4096
 // blocks taking a ticket from ONE counter serialise at ~90 arrivals per microsecond: +0.7 ms per training step.)
-LOCATE_API int locate_gate_bwd(const float* x, const float* a, int a_per_plane, const float* gamma, const float* g,
-                               float* dx, float* da, float* dgamma, int64_t planes, int hw, void* workspace,
-                               int accumulate_dx, void* da_absmax, void* stream) {
-    LOCATE_REQUIRE(planes > 0 && hw > 0 && workspace, "locate_gate_bwd: bad shape or missing workspace");
-    double* block_x2g = static_cast<double*>(workspace);
-    const int64_t blocks = gate_bwd_blocks(planes, hw);          // (what the caller sized its partial sums for)
-    if (hw == 1 && (planes & 63) == 0) {
-        // a 1x1 map (either form of the gate value: a, da are [planes] both ways) IS the element-wise form over "planes" of 64
-        // values each: the several-planes-per-wave kernel instead of one wave per single element (25 us for the 98 304 values of
-        // the deepest block)
-        if (a_per_plane) { a_per_plane = 0; da_absmax = nullptr; }
-        planes >>= 6; hw = 64;
-    }
+template <int TERM>
+static void gate_bwd_launch(const float* x, const float* a, int a_per_plane, const float* gamma, const float* g, float* dx, float* da,
+                            double* block_x2g, int64_t planes, int hw, int64_t blocks, int accumulate_dx, void* da_absmax,
+                            const LocateGateTerm& t, hipStream_t st) {
     const bool whole_block = hw >= 1024;
-    const bool vec = (hw & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx) |
-                                        (a_per_plane ? 0 : (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(da)))) & 15) == 0;
-#define GATE_SMALL(LPV) gate_bwd_small_kernel<LPV><<<(int)blocks, 256, 0, as_stream(stream)>>>(x, a, gamma, g, dx, a_per_plane ? nullptr : da, \
-        a_per_plane ? da : nullptr, block_x2g, planes, hw, a_per_plane, accumulate_dx, static_cast<unsigned*>(da_absmax))
+    uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx) |
+                     (a_per_plane ? 0 : (reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(da)));
+    if (gate_term_is_norm(TERM)) bits |= reinterpret_cast<uintptr_t>(t.go);
+    const bool vec = (hw & 3) == 0 && (bits & 15) == 0;
+    if constexpr (gate_term_is_norm(TERM)) {
+        if (planes != (int64_t)t.B * t.C) {          // the 1x1 map as planes of 64: hw == 64, full-map a
+            if (vec)
+                gate_bwd_small_kernel<16, TERM, true><<<(int)blocks, 256, 0, st>>>(x, a, gamma, g, dx, da, nullptr, block_x2g, planes, hw, 0,
+                                                                                  accumulate_dx, static_cast<unsigned*>(da_absmax), t);
+            else
+                gate_bwd_plane_kernel<1, TERM, true><<<(int)blocks, 256, 0, st>>>(x, a, gamma, g, dx, da, nullptr, block_x2g, planes, hw, 0,
+                                                                                 accumulate_dx, static_cast<unsigned*>(da_absmax), t);
+            return;
+        }
+    }
+#define GATE_SMALL(LPV) gate_bwd_small_kernel<LPV, TERM><<<(int)blocks, 256, 0, st>>>(x, a, gamma, g, dx, a_per_plane ? nullptr : da, \
+        a_per_plane ? da : nullptr, block_x2g, planes, hw, a_per_plane, accumulate_dx, static_cast<unsigned*>(da_absmax), t)
     if (vec && hw <= 128) {
         const int q4 = hw >> 2;
         if (q4 <= 1) GATE_SMALL(1);
@@ -560,18 +711,67 @@ LOCATE_API int locate_gate_bwd(const float* x, const float* a, int a_per_plane, 
         else if (q4 <= 16) GATE_SMALL(16);
         else GATE_SMALL(32);
     } else if (whole_block)
-        gate_bwd_plane_kernel<4><<<(int)blocks, 256, 0, as_stream(stream)>>>(x, a, gamma, g, dx, a_per_plane ? nullptr : da,
-                                                                            a_per_plane ? da : nullptr, block_x2g, planes, hw,
-                                                                            a_per_plane, accumulate_dx, static_cast<unsigned*>(da_absmax));
+        gate_bwd_plane_kernel<4, TERM><<<(int)blocks, 256, 0, st>>>(x, a, gamma, g, dx, a_per_plane ? nullptr : da,
+                                                                   a_per_plane ? da : nullptr, block_x2g, planes, hw,
+                                                                   a_per_plane, accumulate_dx, static_cast<unsigned*>(da_absmax), t);
     else
-        gate_bwd_plane_kernel<1><<<(int)blocks, 256, 0, as_stream(stream)>>>(x, a, gamma, g, dx, a_per_plane ? nullptr : da,
-                                                                            a_per_plane ? da : nullptr, block_x2g, planes, hw,
-                                                                            a_per_plane, accumulate_dx, static_cast<unsigned*>(da_absmax));
+        gate_bwd_plane_kernel<1, TERM><<<(int)blocks, 256, 0, st>>>(x, a, gamma, g, dx, a_per_plane ? nullptr : da,
+                                                                   a_per_plane ? da : nullptr, block_x2g, planes, hw,
+                                                                   a_per_plane, accumulate_dx, static_cast<unsigned*>(da_absmax), t);
+#undef GATE_SMALL
+}
+
+// term.kind == GATE_TERM_NONE: g is the gradient w.r.t. the gate's output (locate_gate_bwd).
+// GATE_TERM_NORM: that gradient is norm_dx(out, term.go) (+ g, the other consumer's share, with term.has_share; g is not read
+//   otherwise) - what locate_norm_bwd_fused's dx launch would have accumulated into g, formed from the plane pass's records
+//   (locate_norm_bwd_planes) - with the norm's [B, C, hw] view of the tensor: B * C == planes.
+// GATE_TERM_ROOTTANH: that gradient is RootTanh'(out) g (locate_roottanh_bwd).
+LOCATE_API int locate_gate_bwd_term(const float* x, const float* a, int a_per_plane, const float* gamma, const float* g,
+                                    float* dx, float* da, float* dgamma, int64_t planes, int hw, void* workspace,
+                                    int accumulate_dx, void* da_absmax, LocateGateTerm term, void* stream) {
+    LOCATE_REQUIRE(planes > 0 && hw > 0 && workspace, "locate_gate_bwd: bad shape or missing workspace");
+    LOCATE_REQUIRE(term.kind == GATE_TERM_NONE || term.kind == GATE_TERM_NORM || term.kind == GATE_TERM_ROOTTANH,
+                   "locate_gate_bwd_term: unknown term %d", term.kind);
+    if (term.kind == GATE_TERM_NORM) {
+        LOCATE_REQUIRE(term.go && term.stats && term.scale && term.partial && term.npartial > 0 && (!term.with_act || term.bias),
+                       "locate_gate_bwd_term: the norm term needs go, stats, scale, the plane pass's partials (and the bias with_act)");
+        LOCATE_REQUIRE(term.groups >= 1 && term.groups <= NORM_MAX_GROUPS && term.B > 0 && term.C > 0 && term.B % term.groups == 0 &&
+                       (int64_t)term.B * term.C == planes && planes * hw < (1ll << 31), "locate_gate_bwd_term: the norm's B x C must be the gate's planes");
+        LOCATE_REQUIRE(!term.has_share || g, "locate_gate_bwd_term: has_share needs the share in g");
+    } else {
+        LOCATE_REQUIRE(g, "locate_gate_bwd_term: missing gradient");
+    }
+    double* block_x2g = static_cast<double*>(workspace);
+    const int64_t blocks = gate_bwd_blocks(planes, hw);          // (what the caller sized its partial sums for)
+    if (hw == 1 && (planes & 63) == 0) {
+        // a 1x1 map (either form of the gate value: a, da are [planes] both ways) IS the element-wise form over "planes" of 64
+        // values each: the several-planes-per-wave kernel instead of one wave per single element (25 us for the 98 304 values of
+        // the deepest block).  (A norm term keeps indexing channel, group and scale by the ORIGINAL plane - the element: the
+        // kernels see planes != B * C.)
+        if (a_per_plane) { a_per_plane = 0; da_absmax = nullptr; }
+        planes >>= 6; hw = 64;
+    }
+    hipStream_t st = as_stream(stream);
+    if (term.kind == GATE_TERM_NONE)
+        gate_bwd_launch<GATE_TERM_NONE>(x, a, a_per_plane, gamma, g, dx, da, block_x2g, planes, hw, blocks, accumulate_dx, da_absmax, term, st);
+    else if (term.kind == GATE_TERM_ROOTTANH)
+        gate_bwd_launch<GATE_TERM_ROOTTANH>(x, a, a_per_plane, gamma, g, dx, da, block_x2g, planes, hw, blocks, accumulate_dx, da_absmax, term, st);
+    else if (term.with_act)
+        gate_bwd_launch<GATE_TERM_NORM_ACT>(x, a, a_per_plane, gamma, g, dx, da, block_x2g, planes, hw, blocks, accumulate_dx, da_absmax, term, st);
+    else
+        gate_bwd_launch<GATE_TERM_NORM>(x, a, a_per_plane, gamma, g, dx, da, block_x2g, planes, hw, blocks, accumulate_dx, da_absmax, term, st);
     LOCATE_LAUNCH_CHECK("locate_gate_bwd(plane)");
     if (!dgamma) return LOCATE_OK;       // the caller sums the locate_gate_bwd_partials() doubles in `workspace` itself, or needs none
-    gate_bwd_final_kernel<<<1, 256, 0, as_stream(stream)>>>(block_x2g, dgamma, (int)blocks);
+    gate_bwd_final_kernel<<<1, 256, 0, st>>>(block_x2g, dgamma, (int)blocks);
     LOCATE_LAUNCH_CHECK("locate_gate_bwd(final)");
     return LOCATE_OK;
+}
+
+LOCATE_API int locate_gate_bwd(const float* x, const float* a, int a_per_plane, const float* gamma, const float* g,
+                               float* dx, float* da, float* dgamma, int64_t planes, int hw, void* workspace,
+                               int accumulate_dx, void* da_absmax, void* stream) {
+    LocateGateTerm none = {};
+    return locate_gate_bwd_term(x, a, a_per_plane, gamma, g, dx, da, dgamma, planes, hw, workspace, accumulate_dx, da_absmax, none, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

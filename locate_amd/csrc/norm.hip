@@ -11,9 +11,9 @@
 // All HBM-bound.  Statistics are accumulated in fp64 in a fixed order (no atomics: bit-reproducible).
 #include "common.h"
 #include "finrec.h"
+#include "normterm.h"          // NORM_MAX_GROUPS, norm_go, norm_group_consts, norm_dx
 
 #define NORM_MAX_PARTIALS 512
-#define NORM_MAX_GROUPS 4
 
 // ---------------------------------------------------------------------------------------------
 // statistics: partial (sum, sum of squares) per block in double; blockIdx.y = group
@@ -190,13 +190,7 @@ LOCATE_API int locate_norm_fwd(const float* x, const float* scale, int scale_per
 //   pass 2 (one block):            dbias[c], dscale, consts[g] = { mean(y go / s_g), dz_g / ((N_g - 1) s_g) }
 //   pass 3 (element-wise):         dx = y[p] go / s_g - consts[g][0] + consts[g][1] (x - mu_g)
 // ---------------------------------------------------------------------------------------------
-template <bool ACT>
-__device__ __forceinline__ float norm_go(float xv, float gv, float mu, float inv_s, float y, float b) {
-    if (!ACT) return gv;
-    const float o = fmaf(xv - mu, y * inv_s, b);          // the same expression as the forward's norm_apply_fused_kernel
-    return roottanh_grad_f(o, gv);
-}
-
+// (norm_go, norm_group_consts, norm_dx: normterm.h - shared with the gate backward kernels that form dx on the fly)
 // y[p] * (S1[p], S2[p]) under a scale y that is not finite.  The reference multiplies the scale into every element BEFORE it sums
 // (xg = y g / s and its mean; dz = -sum((x - mu) g y) / s^2): gradients of both signs under an infinite scale make those sums NaN
 // where y * S is an Inf.  One lane walks the plane - nothing is left of such a run, only the class has to be the reference's.  A
@@ -476,20 +470,8 @@ __global__ void __launch_bounds__(256) norm_bwd_dx_kernel(const float* __restric
     const int grp = blockIdx.y;
     const float mu = stats[2 * grp], s = stats[2 * grp + 1];
     const int64_t n = planes_g * hw;
-    if (threadIdx.x < 64) {           // { mean(y go / s), dz / ((N - 1) s) } of this group from the per-block partials
-        double a = 0.0, b2 = 0.0;
-        for (int i = threadIdx.x; i < npartial; i += 64) {
-            a += partial[((int64_t)i * NORM_MAX_GROUPS + grp) * 2];
-            b2 += partial[((int64_t)i * NORM_MAX_GROUPS + grp) * 2 + 1];
-        }
-        a = wave_sum_d(a);
-        b2 = wave_sum_d(b2);
-        if (threadIdx.x == 0) {
-            const double sd = (double)s, nn = (double)n;
-            consts[0] = (float)(a / sd / nn);
-            consts[1] = (float)(-b2 / (sd * sd) / ((nn - 1.0) * sd));
-        }
-    }
+    // { mean(y go / s), dz / ((N - 1) s) } of this group from the per-block partials
+    if (threadIdx.x < 64) norm_group_consts(partial, npartial, grp, s, n, (int)threadIdx.x, consts);
     __syncthreads();
     const float m = consts[0], k = consts[1];
     const float inv_s = 1.0f / s;
@@ -506,13 +488,10 @@ __global__ void __launch_bounds__(256) norm_bwd_dx_kernel(const float* __restric
             const int c = (int)((unsigned)p % (unsigned)C);
             const float y = scale[scale_per_sample ? p : c], b = ACT ? bias[c] : 0.0f;
             const float4 xv = x4[i];
-            float4 gv = g4[i];
-            gv.x = norm_go<ACT>(xv.x, gv.x, mu, inv_s, y, b); gv.y = norm_go<ACT>(xv.y, gv.y, mu, inv_s, y, b);
-            gv.z = norm_go<ACT>(xv.z, gv.z, mu, inv_s, y, b); gv.w = norm_go<ACT>(xv.w, gv.w, mu, inv_s, y, b);
+            const float4 gv = g4[i];
             float4 o;
-            const float ys = y * inv_s;
-            o.x = fmaf(ys, gv.x, fmaf(k, xv.x - mu, -m)); o.y = fmaf(ys, gv.y, fmaf(k, xv.y - mu, -m));
-            o.z = fmaf(ys, gv.z, fmaf(k, xv.z - mu, -m)); o.w = fmaf(ys, gv.w, fmaf(k, xv.w - mu, -m));
+            o.x = norm_dx<ACT>(xv.x, gv.x, mu, inv_s, y, b, k, m); o.y = norm_dx<ACT>(xv.y, gv.y, mu, inv_s, y, b, k, m);
+            o.z = norm_dx<ACT>(xv.z, gv.z, mu, inv_s, y, b, k, m); o.w = norm_dx<ACT>(xv.w, gv.w, mu, inv_s, y, b, k, m);
             if (accumulate) { const float4 old = o4[i]; o.x += old.x; o.y += old.y; o.z += old.z; o.w += old.w; }
             o4[i] = o;
         }
@@ -522,8 +501,7 @@ __global__ void __launch_bounds__(256) norm_bwd_dx_kernel(const float* __restric
         const int64_t p = plane0 + i / hw;
         const int c = (int)(p % C);
         const float y = scale[scale_per_sample ? p : c];
-        const float gv = norm_go<ACT>(x[i], g[i], mu, inv_s, y, ACT ? bias[c] : 0.0f);
-        const float o = fmaf(y * inv_s, gv, fmaf(k, x[i] - mu, -m));
+        const float o = norm_dx<ACT>(x[i], g[i], mu, inv_s, y, ACT ? bias[c] : 0.0f, k, m);
         dx[i] = accumulate ? dx[i] + o : o;
     }
 }
@@ -589,9 +567,9 @@ LOCATE_API size_t locate_norm_bwd_fused_workspace_bytes(int B, int C) {
 LOCATE_API size_t locate_norm_bwd_fused_plane_offset(void) { return (size_t)NBF_BLOCKS * NORM_MAX_GROUPS * 2 * sizeof(double); }
 
 // dscale_sample: [B*C] when scale_per_sample (written), else must be null (the per-channel dscale comes from the finaliser)
-LOCATE_API int locate_norm_bwd_fused(const float* x, const float* g, const float* stats, const float* scale, int scale_per_sample,
-                                     const float* bias, int with_act, float* dx, float* dscale_sample, int B, int C, int hw,
-                                     int groups, void* workspace, int accumulate_dx, void* stream) {
+static int norm_bwd_fused(const float* x, const float* g, const float* stats, const float* scale, int scale_per_sample,
+                          const float* bias, int with_act, float* dx, float* dscale_sample, int B, int C, int hw,
+                          int groups, void* workspace, int accumulate_dx, void* stream, bool plane_only) {
     LOCATE_REQUIRE(B > 0 && C > 0 && hw > 0 && workspace, "locate_norm_bwd_fused: bad shape or missing workspace");
     LOCATE_REQUIRE(groups >= 1 && groups <= NORM_MAX_GROUPS && B % groups == 0, "locate_norm_bwd_fused: bad group count");
     LOCATE_REQUIRE(!with_act || bias, "locate_norm_bwd_fused: with_act needs the bias");
@@ -613,6 +591,7 @@ LOCATE_API int locate_norm_bwd_fused(const float* x, const float* g, const float
     else
         norm_bwd_plane_kernel<false><<<(int)blocks, 256, 0, st>>>(x, g, stats, scale, scale_per_sample, bias, C, S1, S2, planes, planes_g, hw, partial, dscale_sample);
     LOCATE_LAUNCH_CHECK("locate_norm_bwd_fused(plane)");
+    if (plane_only) return LOCATE_OK;
     const dim3 grid(stream_grid(planes_g * hw, 1024), groups);
     if (with_act)
         norm_bwd_dx_kernel<true><<<grid, 256, 0, st>>>(x, g, stats, scale, scale_per_sample, bias, partial, (int)blocks, dx, planes_g, C, hw, accumulate_dx);
@@ -620,6 +599,27 @@ LOCATE_API int locate_norm_bwd_fused(const float* x, const float* g, const float
         norm_bwd_dx_kernel<false><<<grid, 256, 0, st>>>(x, g, stats, scale, scale_per_sample, bias, partial, (int)blocks, dx, planes_g, C, hw, accumulate_dx);
     LOCATE_LAUNCH_CHECK("locate_norm_bwd_fused(dx)");
     return LOCATE_OK;
+}
+
+LOCATE_API int locate_norm_bwd_fused(const float* x, const float* g, const float* stats, const float* scale, int scale_per_sample,
+                                     const float* bias, int with_act, float* dx, float* dscale_sample, int B, int C, int hw,
+                                     int groups, void* workspace, int accumulate_dx, void* stream) {
+    return norm_bwd_fused(x, g, stats, scale, scale_per_sample, bias, with_act, dx, dscale_sample, B, C, hw, groups, workspace,
+                          accumulate_dx, stream, false);
+}
+
+// The plane pass of locate_norm_bwd_fused alone: S1 / S2, the per-sample scale gradient and the per-block group sums, exactly as
+// that call leaves them - dx is formed by the kernel that consumes it (locate_gate_bwd_term), which adds up the first
+// locate_norm_bwd_fused_partials(B, C) block records at the start of `workspace` the way the dx kernel does.
+LOCATE_API int locate_norm_bwd_fused_partials(int B, int C) {
+    const int64_t blocks = cdiv64((int64_t)B * C, 4);
+    return (int)(blocks > NBF_BLOCKS ? NBF_BLOCKS : blocks);
+}
+LOCATE_API int locate_norm_bwd_planes(const float* x, const float* g, const float* stats, const float* scale, int scale_per_sample,
+                                      const float* bias, int with_act, float* dscale_sample, int B, int C, int hw, int groups,
+                                      void* workspace, void* stream) {
+    return norm_bwd_fused(x, g, stats, scale, scale_per_sample, bias, with_act, nullptr, dscale_sample, B, C, hw, groups, workspace,
+                          0, stream, true);
 }
 
 // dbias[c] = sum_b S1[b, c];  dscale[c] = sum_b S2[b, c] / std(group of b)   - norm_bwd_final_kernel's arithmetic (16 channels x

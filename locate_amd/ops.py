@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from ._lib import check, lib
+from ._lib import GateTerm, check, lib
 
 _IntArr12 = ctypes.c_int * 12
 
@@ -30,6 +30,17 @@ ACT_LINKS = [os.environ.get("LOCATE_ACT_LINKS", "1") != "0"]      # the fused ac
 # (same-box A/B at config 2, bench.py --step-only, two rounds each: off 9.56 / 9.55, up to 0.3 M elements 9.49 / 9.50, 1 M 9.51 /
 # 9.51, 4 M 9.48 / 9.51, 8 M 9.50 / 9.50, every stage 9.54 / 9.54)
 ACT_LINK_MAX_NUMEL = [int(os.environ.get("LOCATE_ACT_LINK_MAX", str(1 << 22)))]
+
+
+# A gate's output feeds the next gate and a norm (every seam between two ResModules), or the output head's RootTanh: that norm's
+# dx / that RootTanh's derivative is then formed inside the gate's own backward kernel (locate_gate_bwd_term, see _GateToken)
+# instead of by an element-wise launch in front of it.  Bit-identical either way; off: today's launches.
+GATE_FOLD = [os.environ.get("LOCATE_GATE_FOLD", "1") != "0"]
+# ... a norm with the fused activation only from this many elements: RootTanh' costs ~30 instructions per element, and below a few
+# million elements the term kernel (77-103 registers, the group constants summed at every block's start) takes longer than the
+# two launches it replaces (profiles/notes_gate_fold.md: 27.8 us against 10.0 + 15.8 at 3 M elements, 17.0 against 6.0 + 6.8
+# on the 2x2 maps; 37.1 against 16.7 + 23.9 at 6 M).  The plain norm and the RootTanh head gain at every size of the step.
+GATE_FOLD_ACT_MIN_NUMEL = [int(os.environ.get("LOCATE_GATE_FOLD_ACT_MIN", str(1 << 22)))]
 
 
 class ActLink:
@@ -220,8 +231,9 @@ def tag_amax(t):
 # ------------------------------------------------------------------------------------------------
 class RootTanhFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, slot=None, amax=None):
+    def forward(ctx, x, slot=None, amax=None, token=None):
         ctx.slot = slot
+        ctx.token = token
         x = _c(x, "root_tanh input")
         y = torch.empty_like(x)
         check(lib().locate_roottanh_fwd(_p(x), _p(y), x.numel(), _p(amax), _stream()), "locate_roottanh_fwd")
@@ -232,6 +244,11 @@ class RootTanhFn(torch.autograd.Function):
     def backward(ctx, g):
         x, = ctx.saved_tensors
         g = _c(g)
+        token = ctx.token
+        if token is not None and token.record is None and GATE_FOLD[0] and token.rt.defer_finalisers and ctx.slot is None:
+            # x is a gate's output and this is its one consumer: the gate's backward kernel multiplies by RootTanh'(x) itself
+            token.leave(_FoldRecord(GateTerm.ROOTTANH, g, (g,)))
+            return g, None, None, None
         gx, acc = ctx.slot.claim(x) if ctx.slot is not None else (torch.empty_like(x), 0)
         # a fresh buffer of its own: its largest magnitude rides along for the contraction that consumes it (a shared fan-out
         # buffer does not get one - the other branch still adds into it)
@@ -240,7 +257,7 @@ class RootTanhFn(torch.autograd.Function):
         check(lib().locate_roottanh_bwd(_p(x), _p(g), _p(gx), x.numel(), acc, _p(amax), _stream()), "locate_roottanh_bwd")
         if amax is not None:
             _tag(gx, amax)
-        return gx, None, None
+        return gx, None, None, None
 
 
 class TanhFn(torch.autograd.Function):
@@ -298,7 +315,9 @@ def root_tanh(x):
     # the activation in front of a conv: its output's largest magnitude rides along for the contraction's fp16-piece form
     # (only worth a word where a contraction of F16_MIN_FLOPS could follow: 4-d maps, not the style chain's rows)
     amax = AMAX.slot(x.device) if x.dim() >= 3 and x.numel() >= AMAX_MIN_NUMEL[0] else None
-    y = RootTanhFn.apply(x, _slot_of(x) if x.is_contiguous() else None, amax)
+    slot = _slot_of(x) if x.is_contiguous() else None
+    token = _token_of(x) if (slot is None and x.is_cuda and x.is_contiguous()) else None
+    y = RootTanhFn.apply(x, slot, amax, token)
     if amax is not None:
         _tag(y, amax)
     return y
@@ -351,6 +370,7 @@ class Runtime:
         self._fin_slab = []              # packed SlabRec records (convwgrad.hip): the split reductions of its other weight gradients
         self._streams = {}               # streams on which this pass queued deferred work / produced late gradients
         self._homes_taken = set()        # parameters whose bucket home (see _grad_home) a gradient of this pass already occupies
+        self._fold_pending = []          # _FoldRecords left for a gate's backward kernel (see _GateToken) in this pass
 
     # the copy of a network (copy.deepcopy in tests, DP replicas) gets a fresh runtime state, never the streams / tables
     def __deepcopy__(self, memo):
@@ -377,6 +397,9 @@ class Runtime:
         self._keep = []
         self._streams = {}
         self._homes_taken = set()
+        for rec in self._fold_pending:
+            rec.drop()
+        self._fold_pending = []
         AMAX.new_pass()
         self._fin_dots, self._fin_rank1, self._fin_sums, self._fin_chan, self._fin_norm = [], [], [], [], []
         self._fin_wgrad, self._fin_slab = [], []
@@ -439,6 +462,13 @@ class Runtime:
                 param.grad.add_(grad)
         self._homes_taken = set()
         self._finalize_dv()
+        pending, self._fold_pending = self._fold_pending, []
+        left = [rec for rec in pending if not rec.done]
+        for rec in left:
+            rec.drop()
+        if left:
+            raise RuntimeError("gate fold: %d consumer(s) of a gate's output left their input gradient to the gate's backward kernel, "
+                               "which never ran in this pass - that gradient was not computed" % len(left))
 
     _FIN = __import__("struct").Struct("<8Q2q8i")
 
@@ -487,6 +517,11 @@ class Runtime:
     def queue_slab_reduce(self, record, operands):
         self._fin_slab.append(record)
         self._keep.append(operands)
+        self._schedule_end()
+
+    def fold_pending(self, rec):
+        """`rec` must be taken by its gate's backward node before the pass ends (checked by the end-of-pass callback)."""
+        self._fold_pending.append(rec)
         self._schedule_end()
 
     def late_grad(self, param, grad):
@@ -638,13 +673,15 @@ def reset_backward_state(*runtimes):
 class _GradSlot:
     """Gradient buffer shared by the backward kernels of the two consumers of a forked tensor.  claim() hands out the buffer
     and says whether it already holds the other consumer's share (then the kernel accumulates)."""
-    __slots__ = ("buf", "claims")
+    __slots__ = ("buf", "claims", "written", "deferred")
 
     def __init__(self):
         self.buf = None
         self.claims = 0
+        self.written = False          # a consumer's kernel has written (or will have written, in stream order) its share
+        self.deferred = None          # _FoldRecord of the consumer that claimed the buffer without writing (claim_deferred)
 
-    def claim(self, like, shape=None):
+    def _take(self, like, shape):
         shape = tuple(like.shape if shape is None else shape)
         self.claims += 1
         if self.claims > 2:
@@ -652,8 +689,20 @@ class _GradSlot:
                                "must feed exactly one participating consumer")
         if self.buf is None:
             self.buf = like.new_empty(shape)
-            return self.buf, 0
-        return (self.buf if tuple(self.buf.shape) == shape else self.buf.view(shape)), 1
+        return self.buf if tuple(self.buf.shape) == shape else self.buf.view(shape)
+
+    def claim(self, like, shape=None):
+        buf = self._take(like, shape)
+        acc, self.written = int(self.written), True
+        return buf, acc
+
+    def claim_deferred(self, like, rec):
+        """The buffer for a consumer whose share is added LATER, by the kernel that reads the buffer (the forked tensor's producer:
+        `rec`, a _FoldRecord): it does not count as the first writer - the other consumer still writes with accumulate = 0 when it
+        is the first to write - and ForkFn.backward tells the record whether anybody wrote."""
+        buf = self._take(like, None)
+        self.deferred = rec
+        return buf
 
 
 class ForkFn(torch.autograd.Function):
@@ -676,8 +725,20 @@ class ForkFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, ga, gb):
         slot, ctx.slot = ctx.slot, None
-        buf, claims = slot.buf, slot.claims
-        slot.buf, slot.claims = None, 0
+        buf, claims, rec, written = slot.buf, slot.claims, slot.deferred, slot.written
+        slot.buf, slot.claims, slot.deferred, slot.written = None, 0, None, False
+        if rec is not None:
+            # one consumer left its share to the producer's backward kernel (claim_deferred) and delivered the unwritten buffer
+            foreign = [g for g in (ga, gb) if g is not None and g.data_ptr() != buf.data_ptr()]
+            delivered = sum(1 for g in (ga, gb) if g is not None and g.data_ptr() == buf.data_ptr())
+            if delivered != claims or (foreign and written):
+                raise RuntimeError("fork: %d consumer(s) claimed the shared gradient buffer but %d branch(es) delivered it - an "
+                                   "alias of a forked tensor fed more than one op" % (claims, delivered))
+            if foreign:                   # the other consumer took no part: its gradient becomes the buffer's share
+                buf.copy_(foreign[0])
+                written = True
+            rec.has_share = written
+            return buf, None
         if ga is None or gb is None:
             return (gb if ga is None else ga), None
         shared = [g for g in (ga, gb) if buf is not None and g.data_ptr() == buf.data_ptr()]
@@ -699,6 +760,9 @@ def fork(x):
     stats = getattr(x, "_locate_stats", None)      # partial norm statistics left by x's producer (residual_gate)
     if stats is not None:
         a._locate_stats = b._locate_stats = stats
+    token = _token_of(x)                           # ... and its producer's hand-over token (see _GateToken)
+    if token is not None:
+        a._locate_gate = b._locate_gate = token
     return a, b
 
 
@@ -750,13 +814,59 @@ def _slot_of(x):
     return getattr(x, "_locate_slot", None)
 
 
+class _FoldRecord:
+    """What a consumer of a gate's output leaves for the gate's backward kernel instead of launching its own element-wise backward:
+    the term (GateTerm of _lib.py) and `buf`, the tensor it returned as its input gradient - which must be what reaches the gate.
+    `keep`: the term's operands, alive until the gate's launch (also under graph capture)."""
+    __slots__ = ("kind", "buf", "keep", "fields", "has_share", "done", "token", "stream")
+
+    def __init__(self, kind, buf, keep, **fields):
+        self.kind, self.buf, self.keep, self.fields = kind, buf, keep, fields
+        self.has_share = False
+        self.done = False
+        self.token = None
+        self.stream = _stream()
+
+    def drop(self):
+        if self.token is not None and self.token.record is self:
+            self.token.record = None
+        self.keep = self.buf = None
+
+    def term(self):
+        return GateTerm(kind=self.kind, has_share=int(self.has_share), **self.fields)
+
+
+class _GateToken:
+    """Hand-over between a gate and the ONE consumer of its output that can leave its input gradient to the gate's backward kernel
+    (locate_gate_bwd_term).  GateFn.forward puts the token on its output, fork() carries it to both aliases, and the norm
+    (inplace_norm, behind a fork, in its two-launch form) or the RootTanh (root_tanh, sole consumer) that takes that tensor keeps
+    it.  In backward that consumer runs no element-wise launch: it leaves a _FoldRecord here and returns the (shared) buffer, and
+    GateFn.backward - which always runs later - launches the term form.  Checked: the gradient that reaches the gate is the
+    record's buffer, and no record outlives the pass (Runtime._end_of_backward)."""
+    __slots__ = ("rt", "record")
+
+    def __init__(self, rt):
+        self.rt = rt
+        self.record = None
+
+    def leave(self, rec):
+        rec.token = self
+        self.record = rec
+        self.rt.fold_pending(rec)
+
+
+def _token_of(x):
+    return getattr(x, "_locate_gate", None)
+
+
 class InPlaceNormFn(torch.autograd.Function):
     """out = (x - mean(x)) * scale / std(x) + bias with global scalar statistics.  With `with_act` the forward
     returns RootTanh(out) instead; the backward recomputes out on the fly, nothing but x is kept."""
 
     @staticmethod
-    def forward(ctx, x, scale, bias, with_act, groups, pre_partial=None, slot=None, amax=None, rt=None):
+    def forward(ctx, x, scale, bias, with_act, groups, pre_partial=None, slot=None, amax=None, rt=None, token=None):
         ctx.slot = slot
+        ctx.token = token
         ctx.rt = rt or DEFAULT_RUNTIME
         ctx.scale_in, ctx.bias_in = scale, bias            # the parameters themselves (late gradients are assigned to them)
         x = _c(x, "norm input")
@@ -788,7 +898,6 @@ class InPlaceNormFn(torch.autograd.Function):
         x, scale, bias, stats = ctx.saved_tensors
         B, C = x.shape[0], x.shape[1]
         hw = x.numel() // (B * C)
-        dx, acc = ctx.slot.claim(x) if ctx.slot is not None else (torch.empty_like(x), 0)
         rt = ctx.rt
         need_scale, need_bias = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         # Two-launch form: dx (and the per-sample scale gradient) now; the per-channel sums dscale[c] / dbias[c] - parameter
@@ -798,8 +907,22 @@ class InPlaceNormFn(torch.autograd.Function):
         if rt.defer_finalisers and per_channel_scale_ok and (not need_bias or ctx.bias_in.is_leaf):
             ws = _ws(L.locate_norm_bwd_fused_workspace_bytes(B, C), x.device)
             dscale = torch.empty(ctx.scale_shape, dtype=torch.float32, device=x.device) if ctx.per_sample else None
-            check(L.locate_norm_bwd_fused(_p(x), _p(g), _p(stats), _p(scale), int(ctx.per_sample), _p(bias), int(ctx.with_act), _p(dx),
-                                          _p(dscale), B, C, hw, ctx.groups, _p(ws), acc, st), "locate_norm_bwd_fused")
+            token = ctx.token
+            if (token is not None and token.record is None and GATE_FOLD[0] and ctx.slot is not None and ctx.needs_input_grad[0]
+                    and token.rt.defer_finalisers and (not ctx.with_act or x.numel() >= GATE_FOLD_ACT_MIN_NUMEL[0])):
+                # x is a gate's output: the plane pass only - the gate's backward kernel forms dx from its records and adds the
+                # other consumer's share, which the fork buffer holds by then (this norm does not count as its first writer)
+                check(L.locate_norm_bwd_planes(_p(x), _p(g), _p(stats), _p(scale), int(ctx.per_sample), _p(bias), int(ctx.with_act),
+                                               _p(dscale), B, C, hw, ctx.groups, _p(ws), st), "locate_norm_bwd_planes")
+                rec = _FoldRecord(GateTerm.NORM, None, (g, stats, scale, bias, ws), with_act=int(ctx.with_act),
+                                  per_sample=int(ctx.per_sample), go=_p(g), stats=_p(stats), scale=_p(scale), bias=_p(bias), partial=_p(ws),
+                                  npartial=L.locate_norm_bwd_fused_partials(B, C), B=B, C=C, groups=ctx.groups)
+                dx = rec.buf = ctx.slot.claim_deferred(x, rec)
+                token.leave(rec)
+            else:
+                dx, acc = ctx.slot.claim(x) if ctx.slot is not None else (torch.empty_like(x), 0)
+                check(L.locate_norm_bwd_fused(_p(x), _p(g), _p(stats), _p(scale), int(ctx.per_sample), _p(bias), int(ctx.with_act),
+                                              _p(dx), _p(dscale), B, C, hw, ctx.groups, _p(ws), acc, st), "locate_norm_bwd_fused")
             late_scale = _grad_home(rt, ctx.scale_in, ctx.scale_shape) if (need_scale and not ctx.per_sample) else None
             late_bias = _grad_home(rt, ctx.bias_in, ctx.bias_shape) if need_bias else None
             if late_scale is not None or late_bias is not None:
@@ -808,13 +931,14 @@ class InPlaceNormFn(torch.autograd.Function):
                     rt.late_grad(ctx.scale_in, late_scale)
                 if late_bias is not None:
                     rt.late_grad(ctx.bias_in, late_bias)
-            return dx, dscale, None, None, None, None, None, None, None
+            return dx, dscale, None, None, None, None, None, None, None, None
+        dx, acc = ctx.slot.claim(x) if ctx.slot is not None else (torch.empty_like(x), 0)
         dscale = torch.empty(ctx.scale_shape, dtype=torch.float32, device=x.device)
         dbias = torch.empty(ctx.bias_shape, dtype=torch.float32, device=x.device)
         ws = _ws(L.locate_norm_bwd_workspace_bytes(B, C), x.device)
         check(L.locate_norm_bwd(_p(x), _p(g), _p(stats), _p(scale), int(ctx.per_sample), _p(bias), int(ctx.with_act), _p(dx),
                                 _p(dscale), _p(dbias), B, C, hw, ctx.groups, _p(ws), acc, st), "locate_norm_bwd")
-        return dx, dscale, dbias, None, None, None, None, None, None
+        return dx, dscale, dbias, None, None, None, None, None, None, None
 
 
 def inplace_norm(x, scale, bias, with_act=False, runtime=None):
@@ -825,7 +949,10 @@ def inplace_norm(x, scale, bias, with_act=False, runtime=None):
     # the output's largest magnitude for the fp16-piece form of the contraction that consumes it (a conv stage behind
     # norm + RootTanh, the position gate's first 1x1 conv behind a plain norm)
     amax = AMAX.slot(x.device) if x.numel() >= AMAX_MIN_NUMEL[0] else None
-    out = InPlaceNormFn.apply(x, scale, bias, with_act, groups, pre_partial, _slot_of(x) if x.is_contiguous() else None, amax, runtime)
+    slot = _slot_of(x) if x.is_contiguous() else None
+    # x straight from a gate, through a fork: this norm's dx can be left to that gate's backward kernel (see _GateToken)
+    token = _token_of(x) if (slot is not None and x.is_cuda) else None
+    out = InPlaceNormFn.apply(x, scale, bias, with_act, groups, pre_partial, slot, amax, runtime, token)
     if amax is not None:
         _tag(out, amax)
     return out
@@ -838,8 +965,9 @@ class GateFn(torch.autograd.Function):
     """out = (gamma * a + 1) * x;  `a` has x's shape or is [B, C, 1, 1] (one value per plane)."""
 
     @staticmethod
-    def forward(ctx, x, a, gamma, stats_groups=0, holder=None, slot=None, rt=None):
+    def forward(ctx, x, a, gamma, stats_groups=0, holder=None, slot=None, rt=None, token=None):
         ctx.slot = slot
+        ctx.token = token
         ctx.rt = rt or DEFAULT_RUNTIME
         ctx.gamma_param = gamma
         x = _c(x, "gate input")
@@ -867,6 +995,16 @@ class GateFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, a, gamma = ctx.saved_tensors
+        rec = ctx.token.record if ctx.token is not None else None
+        if rec is not None:
+            # a consumer of the output left its input gradient to this kernel (see _GateToken): what arrives must be ITS buffer -
+            # a sum that autograd formed with a further consumer's gradient would lose the term
+            ctx.token.record = None
+            if g.data_ptr() != rec.buf.data_ptr():
+                rec.drop()
+                raise RuntimeError("gate fold: the gradient that reached the gate is not the buffer its output's consumer handed "
+                                   "over - the gate's output fed a further op besides that consumer")
+            rec.done = True
         g = _c(g)
         L = lib()
         rt = ctx.rt
@@ -882,27 +1020,38 @@ class GateFn(torch.autograd.Function):
         ws = _ws(L.locate_gate_bwd_workspace_bytes(planes), x.device)
         # full-map form: da goes straight into the branch's last conv (its data and weight gradients) - with its largest magnitude
         amax = AMAX.slot(x.device) if (not ctx.per_plane and da.numel() >= AMAX_MIN_NUMEL[0]) else None
-        check(L.locate_gate_bwd(_p(x), _p(a), int(ctx.per_plane), _p(gamma), _p(g), _p(dx), _p(da), None if deferred else _p(dgamma),
-                                planes, hw, _p(ws), acc, _p(amax), _stream()), "locate_gate_bwd")
+        if rec is not None:
+            if rec.stream != _stream():           # the operands were allocated on the consumer's stream
+                for t in rec.keep:
+                    t.record_stream(torch.cuda.current_stream())
+            check(L.locate_gate_bwd_term(_p(x), _p(a), int(ctx.per_plane), _p(gamma), _p(g), _p(dx), _p(da), None if deferred else _p(dgamma),
+                                         planes, hw, _p(ws), acc, _p(amax), rec.term(), _stream()), "locate_gate_bwd_term")
+            rec.keep = rec.buf = None
+        else:
+            check(L.locate_gate_bwd(_p(x), _p(a), int(ctx.per_plane), _p(gamma), _p(g), _p(dx), _p(da), None if deferred else _p(dgamma),
+                                    planes, hw, _p(ws), acc, _p(amax), _stream()), "locate_gate_bwd")
         if amax is not None:
             _tag(da, amax)
         if deferred:
             rt.queue_sum(ws, L.locate_gate_bwd_partials(planes, hw), dgamma)
             rt.late_grad(ctx.gamma_param, dgamma.view(ctx.gamma_param.shape))
             dgamma = None
-        return dx, da, dgamma, None, None, None, None
+        return dx, da, dgamma, None, None, None, None, None
 
 
 def residual_gate(x, a, gamma, runtime=None, with_stats=True):
     """out = (gamma a + 1) x.  with_stats: the kernel also leaves the InPlaceNorm statistics partials of `out` (for the
     runtime's current stacked-call grouping) on the result, so that a norm consuming it skips its own statistics pass."""
     slot = _slot_of(x) if x.is_contiguous() else None
-    if not with_stats:
-        return GateFn.apply(x, a, gamma, 0, None, slot, runtime)
+    # the hand-over token for the output's consumer (see _GateToken)
+    token = _GateToken(runtime or DEFAULT_RUNTIME) if (GATE_FOLD[0] and x.is_cuda and torch.is_grad_enabled()) else None
     holder = []
-    out = GateFn.apply(x, a, gamma, (runtime or DEFAULT_RUNTIME).stacked, holder, slot, runtime)
+    out = GateFn.apply(x, a, gamma, (runtime or DEFAULT_RUNTIME).stacked if with_stats else 0, holder if with_stats else None, slot,
+                       runtime, token)
     if holder:
         out._locate_stats = holder[0]
+    if token is not None and out.requires_grad:
+        out._locate_gate = token
     return out
 
 
