@@ -659,6 +659,32 @@ int locate_nn_within(const int8_t* qcodes, const int64_t* qnorms, const int32_t*
                      const int32_t* rflags, int N, int row_bytes, const int64_t* radius2, const int32_t* skip, int32_t* hits, int32_t* covered,
                      void* workspace, void* stream);
 
+/* ---- sums of groups of code rows and their rounded means: the centroid update of an exact k-means in the 8-bit domain
+ *      (csrc/modes.hip; locate_amd/modes.py; the definition in int64 numpy: tests/helpers/modes_model.py).  Integers throughout.
+ *      locate_nn_group_sums: codes int8 [N, row_bytes] as locate_nn_encode writes them, 16-byte aligned, row_bytes a multiple of
+ *      64, at most 262144, N >= 1.  order int32 [M]: image indices, not necessarily distinct; an index outside 0 .. N - 1
+ *      contributes nothing.  starts int32 [K + 1]: group k is order[lo_k : hi_k] with lo_k = clamp(starts[k], 0, M) and hi_k =
+ *      clamp(starts[k + 1], 0, M), empty when hi_k <= lo_k.  starts[0] need not be 0 (what precedes it belongs to no group),
+ *      `starts` need not increase (groups may then overlap; each is summed as defined), and no value of `order` or `starts` makes
+ *      a kernel read outside codes, order or starts.  sums int32 [K, row_bytes]: sums[k][j] = the sum of codes[i][j] over group
+ *      k, a row of zeros for an empty group; every word is written.  1 <= M <= 2^24 - 1 (|sum| <= 128 M < 2^31: exact) and
+ *      1 <= K <= 65535, anything else is refused before a launch.  Two launches, no atomics: a walk over slabs of 64 positions of
+ *      `order` that reads every row once and stores a partial sum wherever a group begins or ends, then per group the sum of its
+ *      partials; two calls give the same words.  `workspace`: locate_nn_group_sums_workspace_bytes(M, K, row_bytes) =
+ *      4 (slots (row_bytes + 1) + 2 (K + 1)) bytes with slots = ceil(M / 64) + K + 1 (0 for sizes that are refused), 16-byte
+ *      aligned; neither it nor sums need be zeroed.  order, starts, sums 4-byte aligned.
+ *      locate_nn_centroids: with n = hi_k - lo_k from `starts` and M as above, row k of codes int8 [K, row_bytes] is, per byte,
+ *      floor((2 sums[k][j] + n) / (2 n)) - FLOOR division, a half goes towards +infinity - for n > 0, which lies in -128 .. 127
+ *      when sums are those of n codes (pad bytes: 0), and row k of `previous` byte for byte for n = 0.  `previous` may be `codes`:
+ *      every byte is read before it is written.  norms int64 [K]: the sum of the squares of the row written; moved int32 [K]: the
+ *      bytes of row k that differ from previous[k] (0 for an empty group).  One launch, a block per row, no atomics.  sums,
+ *      previous and codes 16-byte, norms 8-byte, starts and moved 4-byte aligned; the limits on M, K and row_bytes as above. ---- */
+size_t locate_nn_group_sums_workspace_bytes(int M, int K, int row_bytes);
+int locate_nn_group_sums(const int8_t* codes, int N, int row_bytes, const int32_t* order, int M, const int32_t* starts, int K,
+                         int32_t* sums, void* workspace, void* stream);
+int locate_nn_centroids(const int32_t* sums, const int32_t* starts, int K, int M, int row_bytes, const int8_t* previous,
+                        int8_t* codes, int64_t* norms, int32_t* moved, void* stream);
+
 /* ---- radial power spectrum of image planes (csrc/spectrum.hip; locate_amd/spectrum.py).  Per plane x fp32 [S, S], S in {32, 64,
  *      128, 256}, H = S / 2, against the caller's tables cos_table / sin_table fp32 [S][S] (C[k][j] = cos(2 pi k j / S) w[j], Sn
  *      likewise; 16-byte aligned): Ar[y][k] = sum_x x[y][x] C[k][x], Ai[y][k] = - sum_x x[y][x] Sn[k][x]; Yr[a][k] = sum_y C[a][y]

@@ -199,6 +199,9 @@ PROTOTYPES = {
     "locate_nn_search": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p]),
     "locate_nn_within_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "locate_nn_within": (c_i, [c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
+    "locate_nn_group_sums_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "locate_nn_group_sums": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
+    "locate_nn_centroids": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
 }
 
 
@@ -208,7 +211,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 20
+EXPECTED_ABI = 21
 
 
 _lib = None

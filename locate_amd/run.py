@@ -8,7 +8,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--clip-grad-norm X] [--no-skip-nonfinite] [--max-consecutive-skips 16]
                              [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0] [--neighbours 0] [--neighbours-k 3]
                              [--manifold 0] [--manifold-k 3] [--spectrum-images 0] [--spectrum-window none]
-                             [--msssim-pairs 0]
+                             [--msssim-pairs 0] [--modes 0] [--modes-bins 128] [--modes-images 16384]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -70,7 +70,13 @@ Differences from the reference, all additions:
   * `msssim=` / `--msssim-pairs N` (off by default): after every epoch the multi-scale SSIM between N pairs of generated samples
     (`locate_amd.msssim`) beside that of N pairs of real images: a record in `OUT/error/msssim.json`.  It says how alike the samples
     are, scale by scale; with `--ema-half-life` also how alike the live and the averaged generator's images of the same latents are.
-    The evaluation has no side effect on the training; under data parallelism only rank 0 evaluates."""
+    The evaluation has no side effect on the training; under data parallelism only rank 0 evaluates;
+  * `modes=` / `--modes SAMPLES` (off by default): after every epoch the Number of statistically Different Bins of SAMPLES generated
+    samples (`locate_amd.modes`): `--modes-images` real images are clustered into `--modes-bins` k-means cells, exactly, in the 8-bit
+    domain, the samples are assigned to the cells and every cell's share is tested against the real images', with a real-against-
+    real baseline: a record in `OUT/error/modes.json` and the picture `OUT/{epoch}-modes.png` of the cells' centres, the most
+    under-represented first.  It names the modes that are missing.  The evaluation has no side effect on the training; under
+    data parallelism only rank 0 evaluates."""
 import argparse
 import json
 import os
@@ -259,14 +265,22 @@ class Trainer:
     (written to a .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record -
     without "real", which is the same - goes under "average", and `msssim.evaluate_against(gen, average.generator)`, the two
     generators' images of the same latents against each other, under "average_to_live".  The evaluation leaves weights, u / v and
-    optimizer states untouched.  Under data parallelism only rank 0 should be given one."""
+    optimizer states untouched.  Under data parallelism only rank 0 should be given one.
+
+    modes: a `BinnedModes` whose reference is set, or None (the default: nothing below happens, and every file, record and key is
+    what it is without this argument).  After each epoch's msssim record, `modes.evaluate(gen)` runs on the metric's own fixed
+    latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/modes.json` (written to a .tmp and
+    renamed; a resumed run appends to the list it finds); `out/{e+1}-modes.png` shows the bins' centres in the record's order, the
+    most under-represented first.  With `average`, the averaged generator's record - without the baseline, which is the same - goes
+    under "average".  The evaluation leaves weights, u / v and optimizer states untouched.  Under data parallelism only rank 0
+    should be given one."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
                  print_every_function=None, image_interval_function=None, sampler_options=None, log=None, swd=None,
                  average=None, stats=None, stats_every=16, max_consecutive_skips=16, snapshot=None, rollback_every=256,
                  max_rollbacks=3, spill_every=0, dynamics=None, dynamics_every=0, neighbours=None, manifold=None,
-                 formats=None, formats_every=0, spectrum=None, msssim=None):
+                 formats=None, formats_every=0, spectrum=None, msssim=None, modes=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.batch = pipeline.batch
@@ -302,6 +316,7 @@ class Trainer:
         self.manifold = manifold
         self.spectrum = spectrum
         self.msssim = msssim
+        self.modes = modes
         self.average = average
         self._ema_sampler = None
         if int(stats_every) < 0:
@@ -660,6 +675,21 @@ class Trainer:
             records[-1]["average_to_live"] = self.msssim.evaluate_against(self.gen, self.average.generator)
         return _write_json(path, records)
 
+    def _modes(self, e):
+        """One record of the binned mode coverage into out/error/modes.json (written to a .tmp and renamed), for the metric's own
+        fixed latents, and the picture of the bins' centres; returns the files written."""
+        value = self.modes.evaluate(self.gen)
+        path = os.path.join(self.out, "error", "modes.json")
+        records = []
+        if os.path.exists(path):
+            with open(path) as f:
+                records = json.load(f)
+        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
+        if self.average is not None:
+            average = self.modes.evaluate(self.average.generator)
+            records[-1]["average"] = {k: v for k, v in average.items() if k != "baseline"}
+        return [_write_json(path, records), self.modes.save_picture(os.path.join(self.out, "%d-modes.png" % (e + 1)), value)]
+
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);
         returns the number of iterations run so far.  State is saved after every epoch and when max_iterations stops the run."""
@@ -734,6 +764,8 @@ class Trainer:
                 self.written.append(self._spectrum(e))
             if self.msssim is not None:
                 self.written.append(self._msssim(e))
+            if self.modes is not None:
+                self.written += self._modes(e)
             self.epoch, self.sub = e + 1, 0
             if self.stats is not None:
                 self._check_stats(before_save=True)
@@ -806,6 +838,12 @@ def parser():
     ap.add_argument("--msssim-pairs", type=int, default=0, metavar="N",
                     help="after every epoch, the multi-scale SSIM between N pairs of generated samples beside that of N pairs of real "
                          "images (OUT/error/msssim.json): how alike the samples are, scale by scale; image sizes 32, 64, 128, 256; 0: off")
+    ap.add_argument("--modes", type=int, default=0, metavar="SAMPLES",
+                    help="after every epoch, the Number of statistically Different Bins of SAMPLES generated samples against the "
+                         "k-means cells of real images, exact in the 8-bit domain, with a real-against-real baseline "
+                         "(OUT/error/modes.json, OUT/EPOCH-modes.png): which modes are missing; 0: off")
+    ap.add_argument("--modes-bins", type=int, default=128, metavar="K", help="k-means cells, 1 .. --modes-images")
+    ap.add_argument("--modes-images", type=int, default=16384, metavar="IMAGES", help="real images that are clustered")
     return ap
 
 
@@ -828,6 +866,10 @@ def main(argv=None):
         ap.error("--msssim-pairs must be >= 0")
     if args.msssim_pairs > 0 and args.image_size not in (32, 64, 128, 256):
         ap.error("--msssim-pairs takes --image-size 32, 64, 128 or 256")
+    if args.modes < 0 or args.modes_images < 0:
+        ap.error("--modes and --modes-images must be >= 0")
+    if not 1 <= args.modes_bins <= args.modes_images:
+        ap.error("--modes-bins must be 1 .. --modes-images")
     if args.stats_every < 0:
         ap.error("--stats-every must be >= 0")
     if args.dynamics_every < 0:
@@ -902,6 +944,12 @@ def main(argv=None):
         from .msssim import MultiScaleSSIM
         msssim = MultiScaleSSIM(args.image_size, pairs=args.msssim_pairs, seed=args.seed, chunk=min(64, 2 * args.msssim_pairs) // 2 * 2, device=dev)
         msssim.reference_from_pipeline(pipeline)
+    modes = None
+    if args.modes > 0:
+        from .modes import BinnedModes
+        modes = BinnedModes(args.image_size, bins=args.modes_bins, images=args.modes_images, samples=args.modes, seed=args.seed,
+                            chunk=min(64, args.modes), device=dev)
+        modes.reference_from_store(pipeline.store)
     average = None
     if args.ema_half_life > 0:
         from .average import AveragedGenerator
@@ -927,7 +975,7 @@ def main(argv=None):
                       stats_every=args.stats_every if stats is not None else 16, max_consecutive_skips=args.max_consecutive_skips,
                       snapshot=snapshot, rollback_every=args.rollback_every or 256, max_rollbacks=args.max_rollbacks, spill_every=args.spill_every,
                       dynamics=dynamics, dynamics_every=args.dynamics_every, neighbours=neighbours, manifold=manifold,
-                      formats=formats, formats_every=args.formats_every, spectrum=spectrum, msssim=msssim, sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
+                      formats=formats, formats_every=args.formats_every, spectrum=spectrum, msssim=msssim, modes=modes, sampler_options={"advance_spectral_norm": not args.keep_spectral_norm})
     if args.resume:
         trainer.resume()
     else:
