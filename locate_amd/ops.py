@@ -71,6 +71,15 @@ def _c(t, what="tensor"):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _c16(t, what="tensor"):
+    """_c for the entry points that take 16-byte accesses without a scalar form (RootTanh, tanh, the norm's statistics and apply
+    passes: they refuse any other pointer).  A fresh allocation is aligned and passes through as the object it is; a contiguous
+    view that starts off a 16-byte boundary - a slice of a flat buffer, the second part of a torch.cat(dim=0) backward with an odd
+    element count - is copied once."""
+    t = _c(t, what)
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
 def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
@@ -234,7 +243,7 @@ class RootTanhFn(torch.autograd.Function):
     def forward(ctx, x, slot=None, amax=None, token=None):
         ctx.slot = slot
         ctx.token = token
-        x = _c(x, "root_tanh input")
+        x = _c16(x, "root_tanh input")
         y = torch.empty_like(x)
         check(lib().locate_roottanh_fwd(_p(x), _p(y), x.numel(), _p(amax), _stream()), "locate_roottanh_fwd")
         ctx.save_for_backward(x)
@@ -249,6 +258,7 @@ class RootTanhFn(torch.autograd.Function):
             # x is a gate's output and this is its one consumer: the gate's backward kernel multiplies by RootTanh'(x) itself
             token.leave(_FoldRecord(GateTerm.ROOTTANH, g, (g,)))
             return g, None, None, None
+        g = _c16(g)
         gx, acc = ctx.slot.claim(x) if ctx.slot is not None else (torch.empty_like(x), 0)
         # a fresh buffer of its own: its largest magnitude rides along for the contraction that consumes it (a shared fan-out
         # buffer does not get one - the other branch still adds into it)
@@ -263,7 +273,7 @@ class RootTanhFn(torch.autograd.Function):
 class TanhFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        x = _c(x, "tanh input")
+        x = _c16(x, "tanh input")
         y = torch.empty_like(x)
         check(lib().locate_tanh_fwd(_p(x), _p(y), x.numel(), _stream()), "locate_tanh_fwd")
         ctx.save_for_backward(y)
@@ -272,7 +282,7 @@ class TanhFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         y, = ctx.saved_tensors
-        g = _c(g)
+        g = _c16(g)
         gx = torch.empty_like(y)
         check(lib().locate_tanh_bwd(_p(y), _p(g), _p(gx), y.numel(), _stream()), "locate_tanh_bwd")
         return gx
@@ -869,7 +879,7 @@ class InPlaceNormFn(torch.autograd.Function):
         ctx.token = token
         ctx.rt = rt or DEFAULT_RUNTIME
         ctx.scale_in, ctx.bias_in = scale, bias            # the parameters themselves (late gradients are assigned to them)
-        x = _c(x, "norm input")
+        x = _c16(x, "norm input")
         B, C = x.shape[0], x.shape[1]
         hw = x.numel() // (B * C)
         if B % groups:
@@ -894,7 +904,7 @@ class InPlaceNormFn(torch.autograd.Function):
     def backward(ctx, g):
         L = lib()
         st = _stream()
-        g = _c(g)
+        g = _c16(g)
         x, scale, bias, stats = ctx.saved_tensors
         B, C = x.shape[0], x.shape[1]
         hw = x.numel() // (B * C)

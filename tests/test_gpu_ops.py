@@ -1185,8 +1185,10 @@ def test_forked_tensor_second_backward_kernel_accumulates(first, second):
 @pytest.mark.gpu
 def test_upsample_kernel_variants_agree_bit_for_bit():
     """The three forward kernels of the bilinear x2 upsample (scalar, four-wide, 2 x 8 patch) are picked by width and alignment;
-    they evaluate the same stencil with the same roundings: a tensor wide enough for the patch kernel, and the same values seen
-    through a view whose rows start 4 bytes off 16-byte alignment (scalar kernel), must give identical bits."""
+    they evaluate the same stencil with the same roundings: a tensor wide enough for the patch kernel (W = 16), the same values
+    inside a W = 18 tensor (four-wide kernel) and inside a W = 17 tensor (scalar kernel) must give identical bits wherever the
+    outputs see the same stencil.  All three tensors are fresh, aligned allocations - the kernels are picked by WIDTH here; the
+    alignment clauses of the same predicate are driven by tests/test_gpu_variants.py::test_upsample_forward_variants."""
     from locate_amd import ops
     torch.manual_seed(5)
     x = torch.randn(3, 4, 8, 16, device=dev())
