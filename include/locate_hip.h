@@ -723,6 +723,23 @@ size_t locate_msssim_workspace_bytes(int pairs, int S);
 int locate_msssim_pairs(const int8_t* a, const int32_t* aflags, const int8_t* b, const int32_t* bflags, int pairs, int row_bytes, int S,
                         const double* taps, double* out, void* workspace, void* stream);
 
+/* ---- differentiable augmentation of an image batch and its adjoint (csrc/diffaug.hip; locate_amd/augment.py; the definition in
+ *      float64 numpy: tests/helpers/diffaug_model.py).  x, y fp32 [n, 3, S, S] contiguous, 4-byte aligned (16-byte stores and loads
+ *      where a buffer allows them; the values do not depend on it), S in {32, 64, 128, 256}, n <= 65535; params fp32 [n, 12], one row
+ *      per image: b, s, c, ty, tx, y0, y1, x0, x1, 0, 0, 0 (the integers exact in fp32).  policy: bit 0 colour, bit 1 translation,
+ *      bit 2 cutout - it selects the kernel, and an op that is off reads none of its words and executes none of its arithmetic.
+ *      Forward: z = c (s (x - mu) + mu - M) + M + b with mu the mean over the three channels of a pixel and M the image's mean; w the
+ *      gather z[c, i - ty, j - tx], exactly 0.0 outside the frame; y = keep * w, keep = 0.0f on [y0, y1) x [x0, x1) and 1.0f elsewhere,
+ *      an fp32 multiplication.  Backward: gz[c, p] = keep[p + t] gy[c, p + t] inside the frame, else 0; gx = c s gz + c (1 - s)
+ *      mean_c gz + (1 - c) mean(gz).  M and mean(gz) are float64 sums in one fixed order, divided by 3 S^2 and rounded once to fp32;
+ *      no atomics: an image's result depends on that image and its row alone.  S <= 64 is one launch and needs no workspace (it may
+ *      be null); S >= 128 with colour is two launches through `workspace`: the workspace-bytes call's count, 8-byte aligned, need not
+ *      be zeroed.  No allocation, no host read: legal under stream capture. ---- */
+int locate_diffaug_param_floats(void);
+size_t locate_diffaug_workspace_bytes(int n, int S);
+int locate_diffaug_fwd(const float* x, const float* params, float* y, int n, int S, int policy, void* workspace, void* stream);
+int locate_diffaug_bwd(const float* gy, const float* params, float* gx, int n, int S, int policy, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

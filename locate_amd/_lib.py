@@ -202,6 +202,10 @@ PROTOTYPES = {
     "locate_nn_group_sums_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "locate_nn_group_sums": (c_i, [c_p, c_i, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     "locate_nn_centroids": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "locate_diffaug_param_floats": (c_i, []),
+    "locate_diffaug_workspace_bytes": (c_sz, [c_i, c_i]),
+    "locate_diffaug_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
+    "locate_diffaug_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
 }
 
 
@@ -211,7 +215,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 21
+EXPECTED_ABI = 22
 
 
 _lib = None

@@ -283,6 +283,7 @@ class Trainer:
                  formats=None, formats_every=0, spectrum=None, msssim=None, modes=None):
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
+        self.augment = getattr(step, "augment", None)          # a DiffAugment: its rows are drawn before every iteration
         self.batch = pipeline.batch
         self.epochs = None if epochs is None else int(epochs)
         self.max_iterations = None if max_iterations is None else int(max_iterations)
@@ -406,6 +407,8 @@ class Trainer:
             state["guard"] = {tag: opt.counters_state() for tag, opt in self._guards()}
         if self.snapshot is not None:
             state["rollbacks"] = int(self.rollbacks)
+        if self.augment is not None:
+            state["augment"] = self.augment.state_dict()
         path = os.path.join(self.out, STATE_FILE)
         torch.save(state, path + ".tmp")
         os.replace(path + ".tmp", path)
@@ -448,7 +451,9 @@ class Trainer:
                 opt.load_counters_state(state["guard"][tag])
         if self.snapshot is not None:
             self.rollbacks = int(state.get("rollbacks", 0))
-        self._last_take = self.iterations          # no committed slot yet: the first take is rollback_every iterations away
+        if self.augment is not None and "augment" in state:          # a run that had none: the parameter stream starts here
+            self.augment.load_state_dict(state["augment"])
+        self._last_take = self.iterations         # no committed slot yet: the first take is rollback_every iterations away
         self._last_spill = self.iterations
         return self
 
@@ -465,6 +470,8 @@ class Trainer:
             state["average"] = {"updates": int(self.average.updates), "one_minus_beta": float(self.average.one_minus_beta)}
         if self._guards():
             state["guard"] = {tag: opt.counters_state() for tag, opt in self._guards()}
+        if self.augment is not None:
+            state["augment"] = self.augment.state_dict()
         return state
 
     def _guards(self):
@@ -552,7 +559,9 @@ class Trainer:
         if not self.graphed:
             latent = torch.randn(latent_shape, device=self.device, generator=self._latent_gen)          # main.py:142
             real, aug = self.pipeline.next_batch()
-            return self.loop.iteration(latent, real, aug)
+            return self.loop.iteration(latent, real, aug)          # draws the augmentation's rows itself
+        if self.augment is not None:
+            self.augment.draw()          # the graphs read the rows at a fixed address: whatever was uploaded last
         if self._runner is None:
             from .graph import GraphedTrainStep
             latent = torch.randn(latent_shape, device=self.device, generator=self._latent_gen)
@@ -844,6 +853,9 @@ def parser():
                          "(OUT/error/modes.json, OUT/EPOCH-modes.png): which modes are missing; 0: off")
     ap.add_argument("--modes-bins", type=int, default=128, metavar="K", help="k-means cells, 1 .. --modes-images")
     ap.add_argument("--modes-images", type=int, default=16384, metavar="IMAGES", help="real images that are clustered")
+    ap.add_argument("--diffaugment", default="", metavar="POLICY",
+                    help="differentiable augmentation of every batch the discriminator sees: a comma-separated subset of "
+                         "color,translation,cutout (default: off)")
     return ap
 
 
@@ -888,6 +900,15 @@ def main(argv=None):
         ap.error("--spill-every must be >= 0")
     if args.spill_every > 0 and args.rollback_every <= 0:
         ap.error("--spill-every needs --rollback-every: what goes to disk is the last-good copy")
+    diffaugment = 0
+    if args.diffaugment:
+        from .augment import parse_policy
+        try:
+            diffaugment = parse_policy(args.diffaugment)
+        except ValueError as err:
+            ap.error("--diffaugment: %s" % err)
+        if args.image_size not in (32, 64, 128, 256):
+            ap.error("--diffaugment takes --image-size 32, 64, 128 or 256")
     guarded_step = args.clip_grad_norm is not None or args.no_skip_nonfinite
     if args.rollback_every > 0 and not (args.stats_every > 0 or guarded_step):
         ap.error("--rollback-every needs --stats-every or a guarded optimizer (--clip-grad-norm / --no-skip-nonfinite): "
@@ -908,7 +929,11 @@ def main(argv=None):
         gen_opt = GuardedNadam(gen_opt.param_groups, **guarded)
         dis_opt = GuardedNadam(dis_opt.param_groups, **guarded)
     gen.batched_spectral_norm = dis.batched_spectral_norm = True
-    step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches)
+    augment = None
+    if diffaugment:
+        from .augment import DiffAugment
+        augment = DiffAugment(args.image_size, args.batch, policy=diffaugment, seed=args.seed, device=dev)
+    step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches, augment=augment)
     pipeline = InputPipeline(DeviceImageStore(args.store, dev), args.image_size, args.batch, seed=args.seed)
     if not args.resume:
         os.makedirs(args.out, exist_ok=True)

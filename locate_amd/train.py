@@ -44,8 +44,13 @@ def g_loss(d_fake):
 
 class TrainStep:
     def __init__(self, gen, dis, gen_opt, dis_opt, penalty_gamma=100.0, minibatches=1, reducer_g=None, reducer_d=None,
-                 concurrent_d=False, stacked_d=None, overlap_wgrad=False, d_cut=None):
+                 concurrent_d=False, stacked_d=None, overlap_wgrad=False, d_cut=None, augment=None):
         self.gen, self.dis, self.gen_opt, self.dis_opt = gen, dis, gen_opt, dis_opt
+        # augment: a locate_amd.augment.DiffAugment.  Every batch the discriminator sees - the D-step's three thirds, the G-step's
+        # fake - passes through its random transform T first, and the G-step's gradient flows back through T into the generator.
+        # The caller draws the iteration's rows (augment.draw(); TrainLoop.iteration and Trainer do).  The returned images stay
+        # un-augmented.  None: every launch is what it was.
+        self.augment = augment
         # d_cut = j (data parallel): the stacked D-step's backward runs in two segments cut behind block j - 1 of the
         # discriminator stack (Discriminator.forward(cut_after=j)); the reducer sends the first segment's gradients - the
         # deep layers, ~95 % of D's parameters - while the second segment's backward runs.  Same values as one pass.
@@ -116,18 +121,22 @@ class TrainStep:
         for s in self._streams:
             s.wait_stream(main)
         with torch.cuda.stream(s_real):
-            d_true = dis(real)                     # consumes sigma_1
+            d_true = dis(self._seen(real, 0))      # consumes sigma_1
         with torch.cuda.stream(s_fake):
             with torch.no_grad():
                 generated = gen(latent)
-            d_fake = dis(generated)                # consumes sigma_2
+            d_fake = dis(self._seen(generated, 1)) # consumes sigma_2
         with torch.cuda.stream(s_aug):
-            d_aug = dis(aug)                       # consumes sigma_3
+            d_aug = dis(self._seen(aug, 2))        # consumes sigma_3
         for s in self._streams:
             main.wait_stream(s)
         for t_ in (d_true, d_fake, d_aug, generated):
             t_.record_stream(main)
         return generated, d_true, d_fake, d_aug
+
+    def _seen(self, x, third):
+        """what the discriminator sees of third `third` (0 real, 1 generated, 2 augmented) of the unstacked D-step"""
+        return x if self.augment is None else self.augment.d_third(x, third)
 
     def begin_iteration(self, device):
         """What both generator passes of an iteration (main.py:146 and :164: same latent, same weights) have in common, run
@@ -163,7 +172,10 @@ class TrainStep:
                 generated = self.d_generate(latent)
             B = real.shape[0]
             cut = self.d_cut
-            d_all = dis(torch.cat([real, generated, aug], dim=0), stacked=3, cut_after=cut)   # :149, :150, grad_penalty.py:2
+            seen = torch.cat([real, generated, aug], dim=0)
+            if self.augment is not None:
+                seen = self.augment.d_batch(seen)      # T of the whole [3B] batch in one launch; nothing here needs a gradient
+            d_all = dis(seen, stacked=3, cut_after=cut)   # :149, :150, grad_penalty.py:2
             d_true, d_fake, d_aug = d_all[:B], d_all[B:2 * B], d_all[2 * B:]
             losses, g_t, _, _ = d_loss(d_true, d_fake, d_aug, self.penalty_gamma)
             out = {"d_error": losses[0], "penalty": losses[1], "d_true": d_true.detach().view(-1),
@@ -187,9 +199,9 @@ class TrainStep:
         else:
             if generated is None:
                 generated = self.d_generate(latent)
-            d_true = dis(real)                     # :149
-            d_fake = dis(generated)                # :150 (the reference negates it; the loss kernel takes it raw)
-            d_aug = dis(aug)                       # grad_penalty.py:2
+            d_true = dis(self._seen(real, 0))      # :149
+            d_fake = dis(self._seen(generated, 1)) # :150 (the reference negates it; the loss kernel takes it raw)
+            d_aug = dis(self._seen(aug, 2))        # grad_penalty.py:2
         losses, g_t, g_f, g_a = d_loss(d_true, d_fake, d_aug, self.penalty_gamma)
         if self.reducer_d is not None:
             self.reducer_d.begin()
@@ -215,7 +227,7 @@ class TrainStep:
             for _ in range(self.minibatches):      # :162-169 (same noise, zero_grad inside the loop)
                 gen.zero_grad()
                 fake = gen(latent)
-                d_out = dis(fake)
+                d_out = dis(fake if self.augment is None else self.augment.g_batch(fake))
                 loss, g = g_loss(d_out)
                 if self.reducer_g is not None:
                     self.reducer_g.begin()
@@ -236,7 +248,7 @@ class TrainStep:
         dis = self.dis
         dis.requires_grad_(False)                  # main.py:161
         try:
-            d_out = dis(fake)
+            d_out = dis(fake if self.augment is None else self.augment.g_batch(fake))
             loss, g = g_loss(d_out)
             if self.reducer_g is not None:
                 self.reducer_g.begin()
@@ -289,6 +301,8 @@ class TrainLoop:
         """One batch of the loop; returns the D-step record, plus the G-step record when one ran."""
         self.i += 1
         i, step = self.i, self.step
+        if getattr(step, "augment", None) is not None:
+            step.augment.draw()                                    # this iteration's rows, the D-step's and the G-step's
         out = step.d_forward_backward(latent, real, aug)          # main.py:146-156
         if i % self.miniter == 0:                                  # :158
             step.d_optimizer()                                     # :159
