@@ -76,7 +76,7 @@ class AveragedGenerator:
 
     def __init__(self, gen, beta=None, half_life_images=None, batch=None):
         from .models import Generator
-        from .monitor import _spectral_state
+        from .sampling import _spectral_state
         self.beta, self.one_minus_beta = average_weight(beta, half_life_images, batch)
         dev = next(gen.parameters()).device
         if dev.type != "cuda":

@@ -22,7 +22,8 @@ Memory: the real set is `images` row_bytes(S) bytes (4096 at 64 x 64: 50 MB), a 
 Importing this module does not load the HIP library.  CPU tensors raise TypeError: there is no CPU path."""
 import torch
 
-from .neighbours import NearestNeighbours, _gpu, _ptr, _stream, _triple, encode_images, nearest
+from .neighbours import CanonicalViews, _sample_args, _triple, encode_images, nearest
+from .sampling import FixedLatents, _gpu, _ptr, _stream
 
 COUNTS = ("precise", "recalled", "hit_sum", "covered")
 
@@ -82,7 +83,7 @@ def metrics(counts, m, n, k):
             "coverage": counts["covered"] / n}
 
 
-class ManifoldMetrics:
+class ManifoldMetrics(FixedLatents):
     """Precision, recall, density and coverage of `images` generated samples of size S against `images` real ones, k (1 .. 8).
 
     `reference_from_store(store)` draws `images` distinct store indices from a CPU generator seeded `seed + 7`, encodes those
@@ -97,23 +98,20 @@ class ManifoldMetrics:
     so compare values only between runs with the same chunk.  The fixed latents [images, g_in] are drawn on the device on first
     use from a generator seeded `seed + 8`.  Construction needs no GPU.  Under data parallelism only rank 0 should evaluate."""
 
+    latent_seed = 8
+
     def __init__(self, S, k=3, images=4096, seed=999, chunk=64, device="cuda"):
-        self._views = NearestNeighbours(S, k=k, images=images, seed=seed, chunk=chunk, device=device)          # validates; views and generate()
-        self.S, self.k, self.images, self.seed, self.chunk = self._views.S, self._views.k, self._views.images, self._views.seed, self._views.chunk
-        self.device = self._views.device
+        self.S, self.k, self.images, self.seed, self.chunk = int(S), int(k), int(images), int(seed), int(chunk)
+        self._canonical = _sample_args(self.S, self.k, self.images, self.chunk)
+        FixedLatents.__init__(self, device)
         self.real = None
         self.real_radius = None
         self.real_index = None
         self.baseline = None
-        self._latents = None
 
     @property
     def has_reference(self):
         return self.real is not None
-
-    def _need_gpu(self):
-        if self.device.type != "cuda":
-            raise TypeError("ManifoldMetrics computes on the GPU only; its device is %s" % self.device)
 
     def reference_from_store(self, store):
         """The real set, its radii and - if the store is large enough - the baseline (one small device-to-host copy)."""
@@ -122,14 +120,14 @@ class ManifoldMetrics:
         n = min(self.images, N)
         if n < 1:
             raise ValueError("an empty store")
-        self._views.store, self._views._plan = store, None
+        self._canonical = CanonicalViews(self.S, store)
         order = torch.randperm(N, generator=torch.Generator().manual_seed(self.seed + 7)).tolist()
         self.real_index = order[:n]
-        self.real = encode_images(self._views.canonical_views(self.real_index))
+        self.real = self._canonical.encode(self.real_index)
         self.real_radius = kth_radius(self.real, self.k)
         self.baseline = None
         if N >= 2 * self.images:
-            value = self.between(self._views.canonical_views(order[n:2 * n]))
+            value = self.between(self._canonical.views(order[n:2 * n]))
             self.baseline = {key: value[key] for key in ("precision", "recall", "density", "coverage", "counts")}
         return self
 
@@ -159,23 +157,12 @@ class ManifoldMetrics:
         value["baseline"] = None if self.baseline is None else dict(self.baseline, counts=dict(self.baseline["counts"]))
         return value
 
-    def latents(self, g_in):
-        """The fixed latents [images, g_in], drawn on the device from a generator seeded seed + 8."""
-        if self._latents is None or self._latents.shape[1] != int(g_in):
-            self._need_gpu()
-            rng = torch.Generator(device=self.device)
-            rng.manual_seed(self.seed + 8)
-            self._latents = torch.randn(self.images, int(g_in), device=self.device, generator=rng)
-        return self._latents
-
     def evaluate(self, gen, latents=None):
-        """between() of the generator's images of `latents` (default: the fixed ones) - `NearestNeighbours.generate`: eval mode,
+        """between() of the generator's images of `latents` (default: the fixed ones) - `sampling.sampling`: eval mode,
         no_grad, `chunk` latents per forward, every spectral-norm u / v copied back afterwards.  Returns
           "images" m, "real_images" n, "k"; "precision", "recall", "density", "coverage"; "counts": {"precise", "recalled",
           "hit_sum", "covered"}, the integers they are ratios of; "nonfinite": the number of samples that hold a NaN or an Inf;
           "baseline": the four metrics and "counts" of a second real set against the first, or None."""
         if self.real is None:
             raise RuntimeError("reference_from_store() first")
-        if next(gen.parameters()).device.type != "cuda":
-            raise TypeError("ManifoldMetrics computes on the GPU only; the generator is on %s" % next(gen.parameters()).device)
-        return self.between(self._views.generate(gen, self.latents(gen.g_in) if latents is None else latents))
+        return self.between(self._generate(gen, latents))

@@ -15,9 +15,9 @@ measured as they are - the normalisation makes the value free of scale and offse
 A channel that is constant over all gathered values has deviation 0: the result is then not finite.  It is not guarded.
 
 Importing this module does not load the HIP library.  CPU tensors raise TypeError: there is no CPU path."""
-import ctypes
-
 import torch
+
+from .sampling import FixedLatents, _gpu, _ptr, _stream, batches, plain_batches
 
 PATCH = 7
 K = 3 * PATCH * PATCH
@@ -32,22 +32,6 @@ def pyramid_levels(S, min_size=16):
     while sizes[-1] > min_size:
         sizes.append(sizes[-1] // 2)
     return sizes
-
-
-def _gpu(t, name, dtype=torch.float32):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise TypeError("%s must be a GPU tensor (there is no CPU path); got %s" % (name, t.device if torch.is_tensor(t) else type(t).__name__))
-    if t.dtype != dtype:
-        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    return t.detach().contiguous()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _planes(x, name):
@@ -152,7 +136,7 @@ def sorted_distance(a, b, out=None):
     return out
 
 
-class SlicedWasserstein:
+class SlicedWasserstein(FixedLatents):
     """SWD of a candidate image set against a cached reference set, both of `images` fp32 [3, S, S] images.
 
     All randomness is drawn at construction from ONE CPU `torch.Generator` seeded `seed`, in this order: `directions` (float64
@@ -171,13 +155,15 @@ class SlicedWasserstein:
 
     Under data parallelism only rank 0 should evaluate (as with `Sampler`): the metric runs on one device."""
 
+    latent_seed = 3
+
     def __init__(self, S, images=4096, nhoods_per_image=128, dir_repeats=4, dirs_per_repeat=128, seed=999, chunk=64, device="cuda"):
         self.sizes = pyramid_levels(S)
         self.S, self.images, self.nhoods_per_image = int(S), int(images), int(nhoods_per_image)
         self.dir_repeats, self.dirs_per_repeat, self.seed, self.chunk = int(dir_repeats), int(dirs_per_repeat), int(seed), int(chunk)
         if min(self.images, self.nhoods_per_image, self.dir_repeats, self.dirs_per_repeat, self.chunk) < 1:
             raise ValueError("images, nhoods_per_image, dir_repeats, dirs_per_repeat and chunk must be >= 1")
-        self.device = torch.device(device)
+        FixedLatents.__init__(self, device)
         rng = torch.Generator().manual_seed(self.seed)
         d = torch.randn(K, self.dir_repeats * self.dirs_per_repeat, dtype=torch.float64, generator=rng)
         self.directions = (d / d.square().sum(0, keepdim=True).sqrt()).to(torch.float32)
@@ -186,30 +172,18 @@ class SlicedWasserstein:
         for s in self.sizes:
             for which in ("reference", "candidate"):
                 self.positions[which].append(torch.randint(0, s - PATCH + 1, (n, 2), generator=rng, dtype=torch.int32))
-        self._latents = None
         self._dev = None
         self._reference = None
 
     # ---- device copies, made on first use (construction needs no GPU) ----
     def _device_tables(self):
         if self._dev is None:
-            if self.device.type != "cuda":
-                raise TypeError("SlicedWasserstein computes on the GPU only; its device is %s" % self.device)
+            self._need_gpu()
             R, Dr = self.dir_repeats, self.dirs_per_repeat
             self._dev = {"dirs": [self.directions[:, r * Dr:(r + 1) * Dr].contiguous().to(self.device) for r in range(R)],
                          "reference": [p.to(self.device) for p in self.positions["reference"]],
                          "candidate": [p.to(self.device) for p in self.positions["candidate"]]}
         return self._dev
-
-    def latents(self, g_in):
-        """The fixed candidate latents [N, g_in], drawn on the device from a generator seeded seed + 3."""
-        if self._latents is None or self._latents.shape[1] != int(g_in):
-            if self.device.type != "cuda":
-                raise TypeError("SlicedWasserstein computes on the GPU only; its device is %s" % self.device)
-            rng = torch.Generator(device=self.device)
-            rng.manual_seed(self.seed + 3)
-            self._latents = torch.randn(self.images, int(g_in), device=self.device, generator=rng)
-        return self._latents
 
     # ---- the two halves ----
     def _levels(self, batches):
@@ -281,40 +255,13 @@ class SlicedWasserstein:
     def reference_from_pipeline(self, pipeline):
         """set_reference() with N images of the plain chain: the first output of `InputPipeline.next_batch()`, from a pipeline of
         this metric's own over the same store, seeded seed + 2 - the training pipeline's shuffle is not advanced."""
-        from .data import InputPipeline
-        own = InputPipeline(pipeline.store, self.S, min(pipeline.batch, self.images), seed=self.seed + 2)
-
-        def batches():
-            left = self.images
-            while left > 0:
-                real, _ = own.next_batch()
-                yield real[:left]
-                left -= real.shape[0]
-        return self.set_reference(batches())
+        return self.set_reference(plain_batches(pipeline, self.S, self.images, self.seed, self.images))
 
     def evaluate(self, gen):
         """distance() of the generator's images of the fixed latents: eval mode, no_grad, `chunk` latents per forward.  Every
         spectral-norm u / v is snapshotted before and copied back in place after, and the training mode restored: no side effect
         on the training, eager or replayed.  Call it between two iterations, never inside one."""
-        from .monitor import _spectral_state
         self._need_reference()
-        if next(gen.parameters()).device.type != "cuda":
-            raise TypeError("SlicedWasserstein computes on the GPU only; the generator is on %s" % next(gen.parameters()).device)
-        latents = self.latents(gen.g_in)
-        uv = _spectral_state(gen)
-        was_training = gen.training
-
-        def batches():
-            for at in range(0, self.images, self.chunk):
-                yield gen(latents[at:at + self.chunk])
-
-        with torch.no_grad():
-            saved = [p.detach().clone() for p in uv]
-            gen.eval()
-            try:
-                levels = self._levels(batches())
-            finally:
-                gen.train(was_training)
-                if uv:
-                    torch._foreach_copy_([p.data for p in uv], saved)          # in place: same addresses
+        with self._sampling(gen):
+            levels = self._levels(batches(gen, self.latents(gen.g_in), self.chunk))
         return self._against_reference(levels)

@@ -26,7 +26,8 @@ from statistics import NormalDist
 
 import torch
 
-from .neighbours import BANK_CHUNK, NearestNeighbours, _encode_into, _gpu, _ptr, _stream, _triple, encode_images, nearest
+from .neighbours import CanonicalViews, _sample_args, _triple, encode_images, nearest
+from .sampling import FixedLatents, _gpu, _ptr, _stream
 
 K_MAX = 65535
 M_MAX = (1 << 24) - 1
@@ -167,7 +168,7 @@ def ndb_statistics(real_counts, fake_counts, alpha=0.05):
 BASELINE_KEYS = ("ndb", "ndb_over_k", "js", "missing", "fake_counts")
 
 
-class BinnedModes:
+class BinnedModes(FixedLatents):
     """NDB of `samples` generated samples of size S against `bins` k-means cells of `images` real images.
 
     `reference_from_store(store)` takes the canonical views (as `NearestNeighbours` defines them) of min(images, N) distinct store
@@ -184,9 +185,11 @@ class BinnedModes:
     The fixed latents [samples, g_in] are drawn on the device on first use from a generator seeded `seed + 11`.  Construction needs
     no GPU.  Under data parallelism only rank 0 should evaluate."""
 
+    latent_seed = 11
+
     def __init__(self, S, bins=128, images=16384, samples=4096, iterations=10, alpha=0.05, seed=999, chunk=64, device="cuda"):
-        self._views = NearestNeighbours(S, k=1, images=samples, seed=seed, chunk=chunk, device=device)          # validates; views and generate()
-        self.S, self.samples, self.seed, self.chunk = self._views.S, self._views.images, self._views.seed, self._views.chunk
+        self.S, self.samples, self.seed, self.chunk = int(S), int(samples), int(seed), int(chunk)
+        self._canonical = _sample_args(self.S, 1, self.samples, self.chunk)
         self.bins, self.images, self.iterations, self.alpha = int(bins), int(images), int(iterations), float(alpha)
         if not 1 <= self.bins <= self.images:
             raise ValueError("bins must be 1 .. images, got %d bins for %d images" % (self.bins, self.images))
@@ -196,22 +199,20 @@ class BinnedModes:
             raise ValueError("iterations must be >= 0, got %d" % self.iterations)
         if not 0.0 < self.alpha < 1.0:
             raise ValueError("alpha must lie in (0, 1), got %r" % (alpha,))
-        self.device = self._views.device
+        FixedLatents.__init__(self, device)
         self.centres = None
         self.real_index = None
         self.real_counts = None
         self.inertia = None
         self.converged_at = None
         self.baseline = None
-        self._latents = None
+
+    def _latent_count(self):
+        return self.samples
 
     @property
     def has_reference(self):
         return self.centres is not None
-
-    def _need_gpu(self):
-        if self.device.type != "cuda":
-            raise TypeError("BinnedModes computes on the GPU only; its device is %s" % self.device)
 
     def reference_from_store(self, store):
         """The real set, its bins and - if the store is large enough - the baseline (two small device-to-host copies: the flags at
@@ -221,16 +222,10 @@ class BinnedModes:
         n = min(self.images, N)
         if n < self.bins:
             raise ValueError("%d bins from a store of %d images" % (self.bins, N))
-        self._views.store, self._views._plan = store, None
-        dev = store.device
+        self._canonical = CanonicalViews(self.S, store)
         order = torch.randperm(N, generator=torch.Generator().manual_seed(self.seed + 10)).tolist()
         self.real_index = order[:n]
-        rb = self._views.row_bytes
-        real = (torch.empty(n, rb, dtype=torch.int8, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
-                torch.empty(n, dtype=torch.int32, device=dev))
-        for a in range(0, n, BANK_CHUNK):
-            b = min(a + BANK_CHUNK, n)
-            _encode_into(self._views.canonical_views(self.real_index[a:b]), real[0][a:b], real[1][a:b], real[2][a:b])
+        real = self._canonical.encode(self.real_index)
         self.centres, _, counts, inertia, moved = kmeans_codes(real, self.bins, iterations=self.iterations, seed=self.seed + 12)
         still = (moved == 0).all(dim=1).to(torch.int64)
         host = torch.cat([counts.to(torch.int64), inertia, still]).cpu().tolist()          # the one host copy
@@ -239,7 +234,7 @@ class BinnedModes:
         self.converged_at = next((i + 1 for i, s in enumerate(host[K + self.iterations + 1:]) if s), None)
         self.baseline = None
         if N >= self.images + self.samples:
-            value = self.between(self._views.canonical_views(order[n:n + self.samples]))
+            value = self.between(self._canonical.views(order[n:n + self.samples]))
             self.baseline = {key: value[key] for key in BASELINE_KEYS}
         return self
 
@@ -264,17 +259,8 @@ class BinnedModes:
         value["baseline"] = None if self.baseline is None else dict(self.baseline, fake_counts=list(self.baseline["fake_counts"]))
         return value
 
-    def latents(self, g_in):
-        """The fixed latents [samples, g_in], drawn on the device from a generator seeded seed + 11."""
-        if self._latents is None or self._latents.shape[1] != int(g_in):
-            self._need_gpu()
-            rng = torch.Generator(device=self.device)
-            rng.manual_seed(self.seed + 11)
-            self._latents = torch.randn(self.samples, int(g_in), device=self.device, generator=rng)
-        return self._latents
-
     def evaluate(self, gen, latents=None):
-        """between() of the generator's images of `latents` (default: the fixed ones) - `NearestNeighbours.generate`: eval mode,
+        """between() of the generator's images of `latents` (default: the fixed ones) - `sampling.sampling`: eval mode,
         no_grad, `chunk` latents per forward, every spectral-norm u / v copied back afterwards.  Returns
           "bins" K, "images" (the real images that are in a bin), "samples" (the batch, flagged ones included), "alpha";
           "ndb", "ndb_over_k", "js", "missing" (`ndb_statistics`; None if no sample is finite);
@@ -284,9 +270,7 @@ class BinnedModes:
           "baseline": {"ndb", "ndb_over_k", "js", "missing", "fake_counts"} of a second real set in the same bins, or None."""
         if self.centres is None:
             raise RuntimeError("reference_from_store() first")
-        if next(gen.parameters()).device.type != "cuda":
-            raise TypeError("BinnedModes computes on the GPU only; the generator is on %s" % next(gen.parameters()).device)
-        return self.between(self._views.generate(gen, self.latents(gen.g_in) if latents is None else latents))
+        return self.between(self._generate(gen, latents))
 
     def centre_images(self):
         """fp32 [K, 3, S, S]: the centres as pictures, (code + 128) / 127.5 - 1."""

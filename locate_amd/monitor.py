@@ -16,6 +16,7 @@ import zlib
 import numpy as np
 import torch
 
+from .sampling import _spectral_state
 
 def grid_geometry(n, S, nrow=8, padding=2):
     """(xmaps, ymaps, GH, GW) of the picture of n images of S x S."""
@@ -135,12 +136,6 @@ def read_png(path):
     if rows[:, 0].any():
         raise ValueError("%s uses row filters; only filter type 0 is read here" % path)
     return rows[:, 1:].reshape(H, W, 4).copy()
-
-
-def _spectral_state(net):
-    """every spectral-norm u and v of the network"""
-    from .nn import SpectralNorm
-    return [p for m in net.modules() if isinstance(m, SpectralNorm) for p in (m.module.weight_u, m.module.weight_v)]
 
 
 class Sampler:

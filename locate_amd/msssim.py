@@ -13,12 +13,11 @@ negative is `clamped` - unrelated images do go negative at the fine levels - so 
 per-level means beside the value.
 
 Importing this module does not load the HIP library.  CPU tensors raise TypeError: there is no CPU path."""
-import ctypes
-
 import numpy as np
 import torch
 
 from .neighbours import _triple, encode_images
+from .sampling import FixedLatents, _ptr, _stream, batches, plain_batches
 
 SIZES = (32, 64, 128, 256)
 LEVELS = 5
@@ -44,14 +43,6 @@ def window_taps(S):
         g = np.exp(-(t * t) / (2.0 * (1.5 * n / TAPS) ** 2))
         taps[l, :n] = g / g.sum()
     return taps
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 _TAPS = {}
@@ -155,7 +146,7 @@ class _Sums:
                 "levels": {"ssim": [v / n if n else nan for v in host[5:5 + LEVELS]], "cs": [v / n if n else nan for v in host[5 + LEVELS:]]}}
 
 
-class MultiScaleSSIM:
+class MultiScaleSSIM(FixedLatents):
     """MS-SSIM of `pairs` image pairs of size S.
 
     A record (`between`, `among`, `evaluate`, `evaluate_against`):
@@ -172,6 +163,8 @@ class MultiScaleSSIM:
     metric's definition as it is of `SlicedWasserstein`'s, InPlaceNorm takes its statistics over the batch it sees.  Compare runs
     only at equal pairs, chunk and size.  Construction needs no GPU.  Under data parallelism only rank 0 should evaluate."""
 
+    latent_seed = 9
+
     def __init__(self, S, pairs=4096, seed=999, chunk=64, device="cuda"):
         self.S = _size(S)
         self.pairs, self.seed, self.chunk = int(pairs), int(seed), int(chunk)
@@ -179,22 +172,11 @@ class MultiScaleSSIM:
             raise ValueError("pairs must be >= 1, got %d" % self.pairs)
         if self.chunk < 2 or self.chunk % 2:
             raise ValueError("chunk must be even and >= 2 (the pairs are formed inside a chunk), got %d" % self.chunk)
-        self.device = torch.device(device)
+        FixedLatents.__init__(self, device)
         self.real = None
-        self._latents = None
 
-    def _need_gpu(self):
-        if self.device.type != "cuda":
-            raise TypeError("MultiScaleSSIM computes on the GPU only; its device is %s" % self.device)
-
-    def latents(self, g_in):
-        """The fixed latents [2 pairs, g_in], drawn on the device from a generator seeded seed + 9."""
-        if self._latents is None or self._latents.shape[1] != int(g_in):
-            self._need_gpu()
-            rng = torch.Generator(device=self.device)
-            rng.manual_seed(self.seed + 9)
-            self._latents = torch.randn(2 * self.pairs, int(g_in), device=self.device, generator=rng)
-        return self._latents
+    def _latent_count(self):
+        return 2 * self.pairs
 
     def _record(self, sums):
         value = sums.record()
@@ -228,43 +210,16 @@ class MultiScaleSSIM:
         """`among` of the first 2 pairs images of the plain chain - the first output of `InputPipeline.next_batch()`, from a pipeline of
         this metric's own over the same store, seeded seed + 2: the training pipeline's shuffle is not advanced -, kept as the
         record's "real".  The images are taken `chunk` at a time, as evaluate() takes the generator's."""
-        from .data import InputPipeline
         self._need_gpu()
-        own = InputPipeline(pipeline.store, self.S, min(pipeline.batch, 2 * self.pairs), seed=self.seed + 2)
-        sums, held, rest = _Sums(), 0, None
-        while held < 2 * self.pairs:
-            real, _ = own.next_batch()
+        sums, rest = _Sums(), None
+        for real in plain_batches(pipeline, self.S, 2 * self.pairs, self.seed, 2 * self.pairs):
             real = real if rest is None else torch.cat([rest, real])
-            real = real[:2 * self.pairs - held]
             whole = real.shape[0] - real.shape[0] % 2
             for at in range(0, whole, self.chunk):
                 self._among(real[at:min(at + self.chunk, whole)], sums)
-            held += whole
             rest = real[whole:]
         self.real = {k: v for k, v in sums.record().items() if k in KEYS}
         return self
-
-    def _run(self, gens, per_chunk):
-        """every generator of `gens` over the fixed latents, `chunk` at a time: eval mode, no_grad, u / v copied back, the mode restored"""
-        from .monitor import _spectral_state
-        for gen in gens:
-            if next(gen.parameters()).device.type != "cuda":
-                raise TypeError("MultiScaleSSIM computes on the GPU only; the generator is on %s" % next(gen.parameters()).device)
-        latents = self.latents(gens[0].g_in)
-        uv = [p for gen in gens for p in _spectral_state(gen)]
-        was_training = [gen.training for gen in gens]
-        with torch.no_grad():
-            saved = [p.detach().clone() for p in uv]
-            for gen in gens:
-                gen.eval()
-            try:
-                for at in range(0, 2 * self.pairs, self.chunk):
-                    per_chunk([gen(latents[at:at + self.chunk]) for gen in gens])
-            finally:
-                for gen, mode in zip(gens, was_training):
-                    gen.train(mode)
-                if uv:
-                    torch._foreach_copy_([p.data for p in uv], saved)          # in place: same addresses
 
     def evaluate(self, gen):
         """The record of the generator's images of the fixed latents, image 2 j against 2 j + 1 inside every chunk: eval mode, no_grad,
@@ -272,7 +227,9 @@ class MultiScaleSSIM:
         u / v is snapshotted before and copied back in place after, and the training mode restored: no side effect on the training,
         eager or replayed.  Call it between two iterations, never inside one."""
         sums = _Sums()
-        self._run([gen], lambda images: self._among(images[0], sums))
+        with self._sampling(gen):
+            for images in batches(gen, self.latents(gen.g_in), self.chunk):
+                self._among(images, sums)
         return self._record(sums)
 
     def evaluate_against(self, gen_a, gen_b):
@@ -282,5 +239,7 @@ class MultiScaleSSIM:
         if gen_a.g_in != gen_b.g_in:
             raise ValueError("the generators take latents of %d and %d" % (gen_a.g_in, gen_b.g_in))
         sums = _Sums()
-        self._run([gen_a, gen_b], lambda images: sums.add(ms_ssim_levels(encode_images(images[0]), encode_images(images[1]))))
+        with self._sampling(gen_a, gen_b):
+            for a, b in batches([gen_a, gen_b], self.latents(gen_a.g_in), self.chunk):
+                sums.add(ms_ssim_levels(encode_images(a), encode_images(b)))
         return sums.record()

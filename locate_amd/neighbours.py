@@ -13,10 +13,10 @@ Everything is computed in the 8-bit domain (csrc/neighbours.hip through the C AB
 Memory: the bank is N row_bytes(S) bytes (CelebA at 64 x 64: 2.4 GB), the search's workspace Q ceil(N / 128) k 8 bytes.
 
 Importing this module does not load the HIP library.  CPU tensors raise TypeError: there is no CPU path."""
-import ctypes
-
 import numpy as np
 import torch
+
+from .sampling import FixedLatents, _gpu, _ptr, _stream
 
 K_MAX = 8
 BANK_CHUNK = 1024          # images per transform call while the bank is built (the entry point takes at most 65535)
@@ -25,22 +25,6 @@ BANK_CHUNK = 1024          # images per transform call while the bank is built (
 def row_bytes(S):
     """Bytes of one code row: 3 S^2 rounded up to a multiple of 64."""
     return (3 * int(S) * int(S) + 63) // 64 * 64
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _gpu(t, name, dtype):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise TypeError("%s must be a GPU tensor (there is no CPU path); got %s" % (name, t.device if torch.is_tensor(t) else type(t).__name__))
-    if t.dtype != dtype:
-        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    return t.detach().contiguous()
 
 
 def _encode_into(x, codes, norms, flags):
@@ -128,50 +112,16 @@ def summary(values):
     return {"min": float(v.min()), "median": float(np.median(v))}
 
 
-class NearestNeighbours:
-    """Nearest training images of `images` generated samples of size S, k (1 .. 8) per sample.
+class CanonicalViews:
+    """The canonical views of a store's images at size S: the centred square of side min(H, W), no flip, no jitter, resized to S by
+    `data.transform`.  State: S, the store (None until one is given) and the cached `data._Plan`."""
 
-    The bank is `reference_from_store(store)`: every store image's canonical view - the centred square of side min(H, W), no flip,
-    no jitter, resized to S by `data.transform` - encoded; it then holds Pillow's bytes minus 128.  N row_bytes(S) bytes of device
-    memory.  Two baselines are computed with it, once, from `images` distinct bank indices drawn from a CPU generator seeded
-    `seed + 5` (`baseline_index`): `real_to_real`, each drawn image's nearest OTHER bank row, and `real_among_themselves`, the nearest
-    other WITHIN the drawn set - the yardstick for the generated set's own diversity at the same set size.
-
-    Reading a record: `generated_to_real.median` far below `real_to_real.median` means memorisation;
-    `generated_to_generated.median` far below `real_among_themselves.median` means collapse.
-
-    `chunk` latents go through the generator per forward in evaluate(): InPlaceNorm takes its statistics over the batch it sees,
-    so compare values only between runs with the same chunk.  The fixed latents [images, g_in] are drawn on the device on first
-    use from a generator seeded `seed + 6`.  Construction needs no GPU.  Under data parallelism only rank 0 should evaluate."""
-
-    def __init__(self, S, k=3, images=64, seed=999, chunk=64, device="cuda"):
-        self.S, self.k, self.images, self.seed, self.chunk = int(S), int(k), int(images), int(seed), int(chunk)
-        if not 1 <= self.k <= K_MAX:
-            raise ValueError("k must be 1 .. %d, got %d" % (K_MAX, self.k))
+    def __init__(self, S, store=None):
+        self.S, self.store, self._plan = int(S), store, None
         if self.S < 4 or self.S % 4 or self.S > 4096:
             raise ValueError("image size %d: the input pipeline writes 16-byte groups, S must be a multiple of 4" % self.S)
-        if self.images < 1 or self.chunk < 1:
-            raise ValueError("images and chunk must be >= 1")
-        self.device = torch.device(device)
-        self.row_bytes = row_bytes(self.S)
-        self.store = None
-        self.bank = None
-        self.baseline_index = None
-        self.real_to_real = None
-        self.real_among_themselves = None
-        self._latents = None
-        self._plan = None
 
-    # ---- the bank -------------------------------------------------------------------------------------------------------------
-    @property
-    def has_reference(self):
-        return self.bank is not None
-
-    def _need_reference(self):
-        if self.bank is None:
-            raise RuntimeError("reference_from_store() first")
-
-    def canonical_views(self, index):
+    def views(self, index):
         """fp32 [n, 3, S, S]: the canonical views of the store images `index` (a sequence of store indices)."""
         from ._lib import lib
         from .data import _Plan, transform, validate
@@ -193,23 +143,86 @@ class NearestNeighbours:
             transform(store, idx_dev, params_dev, n, n, self._plan, self.S, out[a:a + n], None, ws)
         return out
 
+    def encode(self, index):
+        """The (codes, norms, flags) triple of those views, `BANK_CHUNK` views at a time: never more than that many are held in fp32."""
+        if self.store is None:
+            raise RuntimeError("reference_from_store() first")
+        idx = np.asarray(index, dtype=np.int32).reshape(-1)
+        dev = self.store.device
+        codes = torch.empty(idx.size, row_bytes(self.S), dtype=torch.int8, device=dev)
+        norms = torch.empty(idx.size, dtype=torch.int64, device=dev)
+        flags = torch.empty(idx.size, dtype=torch.int32, device=dev)
+        for a in range(0, idx.size, BANK_CHUNK):
+            b = a + BANK_CHUNK
+            _encode_into(self.views(idx[a:b]), codes[a:b], norms[a:b], flags[a:b])
+        return codes, norms, flags
+
+
+def _sample_args(S, k, images, chunk):
+    """The checks `NearestNeighbours`, `ManifoldMetrics` and `BinnedModes` share, in their order; returns the `CanonicalViews`."""
+    if not 1 <= k <= K_MAX:
+        raise ValueError("k must be 1 .. %d, got %d" % (K_MAX, k))
+    views = CanonicalViews(S)
+    if images < 1 or chunk < 1:
+        raise ValueError("images and chunk must be >= 1")
+    return views
+
+
+class NearestNeighbours(FixedLatents):
+    """Nearest training images of `images` generated samples of size S, k (1 .. 8) per sample.
+
+    The bank is `reference_from_store(store)`: every store image's canonical view - the centred square of side min(H, W), no flip,
+    no jitter, resized to S by `data.transform` - encoded; it then holds Pillow's bytes minus 128.  N row_bytes(S) bytes of device
+    memory.  Two baselines are computed with it, once, from `images` distinct bank indices drawn from a CPU generator seeded
+    `seed + 5` (`baseline_index`): `real_to_real`, each drawn image's nearest OTHER bank row, and `real_among_themselves`, the nearest
+    other WITHIN the drawn set - the yardstick for the generated set's own diversity at the same set size.
+
+    Reading a record: `generated_to_real.median` far below `real_to_real.median` means memorisation;
+    `generated_to_generated.median` far below `real_among_themselves.median` means collapse.
+
+    `chunk` latents go through the generator per forward in evaluate(): InPlaceNorm takes its statistics over the batch it sees,
+    so compare values only between runs with the same chunk.  The fixed latents [images, g_in] are drawn on the device on first
+    use from a generator seeded `seed + 6`.  Construction needs no GPU.  Under data parallelism only rank 0 should evaluate."""
+
+    latent_seed = 6
+
+    def __init__(self, S, k=3, images=64, seed=999, chunk=64, device="cuda"):
+        self.S, self.k, self.images, self.seed, self.chunk = int(S), int(k), int(images), int(seed), int(chunk)
+        self._canonical = _sample_args(self.S, self.k, self.images, self.chunk)
+        FixedLatents.__init__(self, device)
+        self.row_bytes = row_bytes(self.S)
+        self.bank = None
+        self.baseline_index = None
+        self.real_to_real = None
+        self.real_among_themselves = None
+
+    # ---- the bank -------------------------------------------------------------------------------------------------------------
+    @property
+    def store(self):
+        return self._canonical.store
+
+    @property
+    def has_reference(self):
+        return self.bank is not None
+
+    def _need_reference(self):
+        if self.bank is None:
+            raise RuntimeError("reference_from_store() first")
+
+    def canonical_views(self, index):
+        """fp32 [n, 3, S, S]: the canonical views of the store images `index` (a sequence of store indices)."""
+        return self._canonical.views(index)
+
     def reference_from_store(self, store, limit=None):
         """The bank: the canonical view of the first `limit` store images (default: all), encoded `BANK_CHUNK` images at a time; then
         the two baselines (one small device-to-host copy)."""
-        if self.device.type != "cuda":
-            raise TypeError("NearestNeighbours computes on the GPU only; its device is %s" % self.device)
+        self._need_gpu()
         N = len(store) if limit is None else min(int(limit), len(store))
         if N < 1:
             raise ValueError("an empty bank")
-        self.store, self._plan = store, None
+        self._canonical = CanonicalViews(self.S, store)
         dev = store.device
-        codes = torch.empty(N, self.row_bytes, dtype=torch.int8, device=dev)
-        norms = torch.empty(N, dtype=torch.int64, device=dev)
-        flags = torch.empty(N, dtype=torch.int32, device=dev)
-        for a in range(0, N, BANK_CHUNK):
-            b = min(a + BANK_CHUNK, N)
-            _encode_into(self.canonical_views(range(a, b)), codes[a:b], norms[a:b], flags[a:b])
-        self.bank = (codes, norms, flags)
+        self.bank = codes, norms, flags = self._canonical.encode(range(N))
         m = min(self.images, N)
         drawn = torch.randperm(N, generator=torch.Generator().manual_seed(self.seed + 5))[:m].to(torch.int32)
         self.baseline_index = drawn.tolist()
@@ -245,39 +258,11 @@ class NearestNeighbours:
         value["nonfinite"] = sum(1 for row in host if row[2 * k + 1] != 0)
         return value
 
-    def latents(self, g_in):
-        """The fixed latents [images, g_in], drawn on the device from a generator seeded seed + 6."""
-        if self._latents is None or self._latents.shape[1] != int(g_in):
-            if self.device.type != "cuda":
-                raise TypeError("NearestNeighbours computes on the GPU only; its device is %s" % self.device)
-            rng = torch.Generator(device=self.device)
-            rng.manual_seed(self.seed + 6)
-            self._latents = torch.randn(self.images, int(g_in), device=self.device, generator=rng)
-        return self._latents
-
     def generate(self, gen, latents=None):
         """fp32 [Q, 3, S, S]: the generator's images of `latents` (default: the fixed ones) - eval mode, no_grad, `chunk` latents per
         forward.  Every spectral-norm u / v is snapshotted before and copied back in place after, and the training mode restored: no
         side effect on the training, eager or replayed.  Call it between two iterations, never inside one."""
-        from .monitor import _spectral_state
-        if next(gen.parameters()).device.type != "cuda":
-            raise TypeError("NearestNeighbours computes on the GPU only; the generator is on %s" % next(gen.parameters()).device)
-        if latents is None:
-            latents = self.latents(gen.g_in)
-        elif not torch.is_tensor(latents) or latents.dim() != 2 or latents.shape[1] != gen.g_in or latents.shape[0] < 1:
-            raise ValueError("latents must be [Q, %d]" % gen.g_in)
-        uv = _spectral_state(gen)
-        was_training = gen.training
-        with torch.no_grad():
-            saved = [p.detach().clone() for p in uv]
-            gen.eval()
-            try:
-                out = torch.cat([gen(latents[at:at + self.chunk]).detach() for at in range(0, latents.shape[0], self.chunk)])
-            finally:
-                gen.train(was_training)
-                if uv:
-                    torch._foreach_copy_([p.data for p in uv], saved)          # in place: same addresses
-        return out
+        return self._generate(gen, latents)
 
     def evaluate(self, gen, latents=None):
         """search() of generate(gen, latents).  Returns

@@ -245,35 +245,18 @@ class Trainer:
     `{e+1}-neighbours.ema.png`.  The evaluation leaves weights, u / v and optimizer states untouched.  Under data parallelism only
     rank 0 should be given one.
 
-    manifold: a `ManifoldMetrics` whose reference is set, or None (the default: nothing below happens, and every file, record and
-    key is what it is without this argument).  After each epoch's neighbours record, `manifold.evaluate(gen)` runs on the metric's own
-    fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/manifold.json` (written to a
-    .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record - without the
-    baseline, which is the same - goes under "average".  The evaluation leaves weights, u / v and optimizer states untouched.
-    Under data parallelism only rank 0 should be given one.
+    manifold, spectrum, msssim, modes: a `ManifoldMetrics` and a `RadialSpectrum` whose reference is set, a `MultiScaleSSIM` (with its
+    "real" reference, if wanted) and a `BinnedModes` whose reference is set, or None each (the default: nothing below happens, and every file, record
+    and key is what it is without that argument).  After each epoch's neighbours record, in this order, the metric's `evaluate(gen)`
+    runs on the metric's own fixed latents and the record, with "epoch" and "iterations", is appended to the list in
+    `out/error/manifold.json`, `spectrum.json`, `msssim.json` and `modes.json` (written to a .tmp and renamed; a resumed run appends to
+    the list it finds).  With `average`, the averaged generator's record - without the baseline (msssim: without "real"), which is the
+    same - goes under "average", and for msssim `msssim.evaluate_against(gen, average.generator)`, the two generators' images of the
+    same latents against each other, under "average_to_live".  For modes, `out/{e+1}-modes.png` shows the bins' centres in the live
+    record's order, the most under-represented first.  The evaluations leave weights, u / v and optimizer states untouched.  Under
+    data parallelism only rank 0 should be given them.
 
-    spectrum: a `RadialSpectrum` whose reference is set, or None (the default: nothing below happens, and every file, record and
-    key is what it is without this argument).  After each epoch's manifold record, `spectrum.evaluate(gen)` runs on the metric's own
-    fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/spectrum.json` (written to a
-    .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record - without the
-    baseline, which is the same - goes under "average".  The evaluation leaves weights, u / v and optimizer states untouched.
-    Under data parallelism only rank 0 should be given one.
-
-    msssim: a `MultiScaleSSIM` (with its "real" reference, if wanted), or None (the default: nothing below happens, and every file,
-    record and key is what it is without this argument).  After each epoch's spectrum record, `msssim.evaluate(gen)` runs on the
-    metric's own fixed latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/msssim.json`
-    (written to a .tmp and renamed; a resumed run appends to the list it finds).  With `average`, the averaged generator's record -
-    without "real", which is the same - goes under "average", and `msssim.evaluate_against(gen, average.generator)`, the two
-    generators' images of the same latents against each other, under "average_to_live".  The evaluation leaves weights, u / v and
-    optimizer states untouched.  Under data parallelism only rank 0 should be given one.
-
-    modes: a `BinnedModes` whose reference is set, or None (the default: nothing below happens, and every file, record and key is
-    what it is without this argument).  After each epoch's msssim record, `modes.evaluate(gen)` runs on the metric's own fixed
-    latents and the record, with "epoch" and "iterations", is appended to the list in `out/error/modes.json` (written to a .tmp and
-    renamed; a resumed run appends to the list it finds); `out/{e+1}-modes.png` shows the bins' centres in the record's order, the
-    most under-represented first.  With `average`, the averaged generator's record - without the baseline, which is the same - goes
-    under "average".  The evaluation leaves weights, u / v and optimizer states untouched.  Under data parallelism only rank 0
-    should be given one."""
+    All six records go through `_append_record`, the one place that reads, appends to and writes a list in `out/error`."""
 
     def __init__(self, step, pipeline, out, epochs=None, max_iterations=None, images=64, seed=999, diters=1, minibatches=None,
                  mean_window=16, graphed=False, fixed_noise=None, miniter_function=None, subepoch_function=None,
@@ -604,100 +587,63 @@ class Trainer:
         if self.average is not None:
             self.written.append(self.ema_sampler.save(path[:-len(".png")] + ".ema.png"))
 
-    def _measure(self, e):
-        """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
-        value = self.swd.evaluate(self.gen)
-        path = os.path.join(self.out, "error", "swd.json")
+    def _append_record(self, name, e, evaluate, keys=None, drop=None, also=None):
+        """One record into the list in out/error/NAME.json (a resumed run appends to the list it finds; written to a .tmp and
+        renamed): "epoch", "iterations" and what evaluate(gen) returns - `keys` of it, if given.  With an average, the same of
+        evaluate(average.generator) without the key `drop` goes under "average", and what also() returns beside it.  Returns the
+        file written and the live generator's value."""
+        value = evaluate(self.gen)
+        path = os.path.join(self.out, "error", name + ".json")
         records = []
         if os.path.exists(path):
             with open(path) as f:
                 records = json.load(f)
-        records.append({"epoch": e + 1, "iterations": self.iterations, "levels": value["levels"], "mean": value["mean"]})
+        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **{k: value[k] for k in keys or value}))
         if self.average is not None:
-            value = self.swd.evaluate(self.average.generator)
-            records[-1]["average"] = {"levels": value["levels"], "mean": value["mean"]}
-        return _write_json(path, records)
+            average = evaluate(self.average.generator)
+            records[-1]["average"] = {k: average[k] for k in keys or average if k != drop}
+            if also is not None:
+                records[-1].update(also())
+        return _write_json(path, records), value
+
+    def _measure(self, e):
+        """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
+        return self._append_record("swd", e, self.swd.evaluate, keys=("levels", "mean"))[0]
 
     def _nearest(self, e):
         """One record of the samples' nearest training images into out/error/neighbours.json (written to a .tmp and renamed) and
         the picture out/error/{e+1}-neighbours.png, for the sampler's fixed latents; returns the files written."""
         keys = ("images", "k", "generated_to_real", "generated_to_generated", "real_to_real", "real_among_themselves", "nonfinite", "index")
-        latents = self.sampler.fixed_noise
-        value = self.neighbours.evaluate(self.gen, latents=latents)
-        path = os.path.join(self.out, "error", "neighbours.json")
-        records = []
-        if os.path.exists(path):
-            with open(path) as f:
-                records = json.load(f)
-        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **{k: value[k] for k in keys}))
-        written = [self.neighbours.save_picture(os.path.join(self.out, "error", "%d-neighbours.png" % (e + 1)), self.gen, latents=latents)]
-        if self.average is not None:
-            value = self.neighbours.evaluate(self.average.generator, latents=latents)
-            records[-1]["average"] = {k: value[k] for k in keys}
-            written.append(self.neighbours.save_picture(os.path.join(self.out, "error", "%d-neighbours.ema.png" % (e + 1)),
-                                                        self.average.generator, latents=latents))
-        return [_write_json(path, records)] + written
+        latents, written = self.sampler.fixed_noise, []
+
+        def evaluate(gen):          # the record, then the picture, of one generator
+            value = self.neighbours.evaluate(gen, latents=latents)
+            name = "%d-neighbours%s.png" % (e + 1, "" if gen is self.gen else ".ema")
+            written.append(self.neighbours.save_picture(os.path.join(self.out, "error", name), gen, latents=latents))
+            return value
+        return [self._append_record("neighbours", e, evaluate, keys=keys)[0]] + written
 
     def _manifold(self, e):
         """One record of precision / recall / density / coverage into out/error/manifold.json (written to a .tmp and renamed), for
         the metric's own fixed latents; returns the file written."""
-        value = self.manifold.evaluate(self.gen)
-        path = os.path.join(self.out, "error", "manifold.json")
-        records = []
-        if os.path.exists(path):
-            with open(path) as f:
-                records = json.load(f)
-        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
-        if self.average is not None:
-            value = self.manifold.evaluate(self.average.generator)
-            records[-1]["average"] = {k: v for k, v in value.items() if k != "baseline"}
-        return _write_json(path, records)
+        return self._append_record("manifold", e, self.manifold.evaluate, drop="baseline")[0]
 
     def _spectrum(self, e):
         """One record of the radial power spectrum into out/error/spectrum.json (written to a .tmp and renamed), for the metric's
         own fixed latents; returns the file written."""
-        value = self.spectrum.evaluate(self.gen)
-        path = os.path.join(self.out, "error", "spectrum.json")
-        records = []
-        if os.path.exists(path):
-            with open(path) as f:
-                records = json.load(f)
-        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
-        if self.average is not None:
-            value = self.spectrum.evaluate(self.average.generator)
-            records[-1]["average"] = {k: v for k, v in value.items() if k != "baseline"}
-        return _write_json(path, records)
+        return self._append_record("spectrum", e, self.spectrum.evaluate, drop="baseline")[0]
 
     def _msssim(self, e):
         """One record of the multi-scale SSIM into out/error/msssim.json (written to a .tmp and renamed), for the metric's own fixed
         latents; returns the file written."""
-        value = self.msssim.evaluate(self.gen)
-        path = os.path.join(self.out, "error", "msssim.json")
-        records = []
-        if os.path.exists(path):
-            with open(path) as f:
-                records = json.load(f)
-        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
-        if self.average is not None:
-            value = self.msssim.evaluate(self.average.generator)
-            records[-1]["average"] = {k: v for k, v in value.items() if k != "real"}
-            records[-1]["average_to_live"] = self.msssim.evaluate_against(self.gen, self.average.generator)
-        return _write_json(path, records)
+        return self._append_record("msssim", e, self.msssim.evaluate, drop="real", also=lambda: {
+            "average_to_live": self.msssim.evaluate_against(self.gen, self.average.generator)})[0]
 
     def _modes(self, e):
         """One record of the binned mode coverage into out/error/modes.json (written to a .tmp and renamed), for the metric's own
         fixed latents, and the picture of the bins' centres; returns the files written."""
-        value = self.modes.evaluate(self.gen)
-        path = os.path.join(self.out, "error", "modes.json")
-        records = []
-        if os.path.exists(path):
-            with open(path) as f:
-                records = json.load(f)
-        records.append(dict({"epoch": e + 1, "iterations": self.iterations}, **value))
-        if self.average is not None:
-            average = self.modes.evaluate(self.average.generator)
-            records[-1]["average"] = {k: v for k, v in average.items() if k != "baseline"}
-        return [_write_json(path, records), self.modes.save_picture(os.path.join(self.out, "%d-modes.png" % (e + 1)), value)]
+        path, value = self._append_record("modes", e, self.modes.evaluate, drop="baseline")
+        return [path, self.modes.save_picture(os.path.join(self.out, "%d-modes.png" % (e + 1)), value)]
 
     def run(self):
         """Runs until `epochs` epochs are done or `max_iterations` iterations have been run in all (counted across resumes);

@@ -13,11 +13,12 @@ A set's summary (`spectrum_summary`) is per channel and bin the sum and the sum 
 azimuthal average - over the planes whose spectrum is finite, and the number of those that are not.
 
 Importing this module does not load the HIP library.  CPU tensors raise TypeError: there is no CPU path."""
-import ctypes
 import math
 
 import numpy as np
 import torch
+
+from .sampling import FixedLatents, _gpu, _ptr, _stream, batches, plain_batches
 
 SIZES = (32, 64, 128, 256)
 WINDOWS = ("none", "hann")
@@ -87,22 +88,6 @@ def dft_tables(S, window="none"):
     c[exact] = np.array([1.0, 0.0, -1.0, 0.0])[quarter]
     s[exact] = np.array([0.0, 1.0, 0.0, -1.0])[quarter]
     return (c * w[None, :]).astype(np.float32), (s * w[None, :]).astype(np.float32)
-
-
-def _gpu(t, name, dtype=torch.float32):
-    if not torch.is_tensor(t) or not t.is_cuda:
-        raise TypeError("%s must be a GPU tensor (there is no CPU path); got %s" % (name, t.device if torch.is_tensor(t) else type(t).__name__))
-    if t.dtype != dtype:
-        raise ValueError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    return t.detach().contiguous()
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 _TABLES = {}
@@ -204,7 +189,7 @@ def gap_record(real, fake, S):
             "high_gap_db": [sum(row[first:]) / len(row[first:]) for row in gaps], "max_abs_gap_db": max(abs(v) for row in gaps for v in row)}
 
 
-class RadialSpectrum:
+class RadialSpectrum(FixedLatents):
     """The radial power spectrum of a candidate image set against a cached real set, both of `images` fp32 [3, S, S] images.
 
     A record (`between`, `distance`, `evaluate`):
@@ -219,6 +204,8 @@ class RadialSpectrum:
     definition as it is of `SlicedWasserstein`'s: InPlaceNorm takes its statistics over the batch it sees.  Construction needs no
     GPU.  Under data parallelism only rank 0 should evaluate."""
 
+    latent_seed = 3
+
     def __init__(self, S, images=4096, seed=999, chunk=64, window="none", device="cuda"):
         self.S = _size(S)
         if window not in WINDOWS:
@@ -226,24 +213,10 @@ class RadialSpectrum:
         self.images, self.seed, self.chunk, self.window = int(images), int(seed), int(chunk), window
         if min(self.images, self.chunk) < 1:
             raise ValueError("images and chunk must be >= 1")
-        self.device = torch.device(device)
+        FixedLatents.__init__(self, device)
         self.bins = int(radial_bins(self.S)[1].size)
         self.baseline = None
-        self._latents = None
         self._reference = None
-
-    def _need_gpu(self):
-        if self.device.type != "cuda":
-            raise TypeError("RadialSpectrum computes on the GPU only; its device is %s" % self.device)
-
-    def latents(self, g_in):
-        """The fixed candidate latents [N, g_in], drawn on the device from a generator seeded seed + 3."""
-        if self._latents is None or self._latents.shape[1] != int(g_in):
-            self._need_gpu()
-            rng = torch.Generator(device=self.device)
-            rng.manual_seed(self.seed + 3)
-            self._latents = torch.randn(self.images, int(g_in), device=self.device, generator=rng)
-        return self._latents
 
     def spectra(self, batches, expect=None):
         """float64 [n, 3, R]: the per-plane spectra of one [n, 3, S, S] tensor or an iterable of such batches."""
@@ -306,13 +279,10 @@ class RadialSpectrum:
         this metric's own over the same store, seeded seed + 2 - the training pipeline's shuffle is not advanced.  The N images that
         follow in the same pass - so disjoint from the first - become the baseline when the store holds at least 2 N images and the
         pass that many in whole batches; else the baseline is None."""
-        from .data import InputPipeline
-        own = InputPipeline(pipeline.store, self.S, min(pipeline.batch, self.images), seed=self.seed + 2)
-        second = len(pipeline.store) >= 2 * self.images and -(-2 * self.images // own.batch) <= own.batches_per_epoch
+        batch = min(pipeline.batch, self.images)
+        second = len(pipeline.store) >= 2 * self.images and -(-2 * self.images // batch) <= len(pipeline.store) // batch
         sets, held = [[], []], 0
-        while held < (2 if second else 1) * self.images:
-            real, _ = own.next_batch()
-            real = real[:(2 if second else 1) * self.images - held]
+        for real in plain_batches(pipeline, self.S, self.images, self.seed, (2 if second else 1) * self.images):
             cut = max(0, min(real.shape[0], self.images - held))          # the part that still belongs to the first set
             if cut:
                 sets[0].append(radial_spectrum(real[:cut], self.window))
@@ -328,26 +298,8 @@ class RadialSpectrum:
         """distance() of the generator's images of the fixed latents: eval mode, no_grad, `chunk` latents per forward.  Every
         spectral-norm u / v is snapshotted before and copied back in place after, and the training mode restored: no side effect
         on the training, eager or replayed.  Call it between two iterations, never inside one."""
-        from .monitor import _spectral_state
         self._need_reference()
-        if next(gen.parameters()).device.type != "cuda":
-            raise TypeError("RadialSpectrum computes on the GPU only; the generator is on %s" % next(gen.parameters()).device)
-        latents = self.latents(gen.g_in)
-        uv = _spectral_state(gen)
-        was_training = gen.training
-
-        def batches():
-            for at in range(0, self.images, self.chunk):
-                yield gen(latents[at:at + self.chunk])
-
-        with torch.no_grad():
-            saved = [p.detach().clone() for p in uv]
-            gen.eval()
-            try:
-                spectra = self.spectra(batches(), self.images)
-            finally:
-                gen.train(was_training)
-                if uv:
-                    torch._foreach_copy_([p.data for p in uv], saved)          # in place: same addresses
+        with self._sampling(gen):
+            spectra = self.spectra(batches(gen, self.latents(gen.g_in), self.chunk), self.images)
         fake, bad = summary_means(spectrum_summary(spectra))
         return self._record(self._reference, fake, self.images, bad)

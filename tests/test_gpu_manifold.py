@@ -362,7 +362,7 @@ def test_evaluate_is_the_model_applied_to_the_generated_images():
     rng = torch.Generator(device=DEV)
     rng.manual_seed(4 + 8)
     assert torch.equal(mm.latents(G.g_in), torch.randn(16, G.g_in, device=DEV, generator=rng))
-    images = mm._views.generate(G, mm.latents(G.g_in))
+    images = mm._generate(G, mm.latents(G.g_in))
     real = tuple(t.cpu().numpy() for t in mm.real)
     assert np.array_equal(real[0], NM.bank_codes(STORE, 32)[mm.real_index])
     assert first == M.between(NM.encode(images.cpu().numpy()), real, 3, mm.baseline)

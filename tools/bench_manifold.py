@@ -106,7 +106,7 @@ def main():
         settings["search_k1_n%d" % n] = lambda n=n: nearest(q, refs[n], k=1)
         settings["aten_n%d" % n] = lambda n=n: aten_within(q, refs[n], radii[n], elems)
     settings["evaluate"] = lambda: mm.evaluate(gen)
-    settings["generate"] = lambda: mm._views.generate(gen, latents)
+    settings["generate"] = lambda: mm._generate(gen, latents)
     rounds = {name: [] for name in settings}
     for _ in range(args.rounds):
         for name, fn in settings.items():

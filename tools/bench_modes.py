@@ -165,7 +165,7 @@ def main():
         gen.batched_spectral_norm = True
         latents = bm.latents(gen.g_in)
         settings["evaluate"] = lambda: bm.evaluate(gen)
-        settings["generate"] = lambda: bm._views.generate(gen, latents)
+        settings["generate"] = lambda: bm._generate(gen, latents)
 
     rounds = {name: [] for name in settings}
     for _ in range(args.rounds):
