@@ -726,7 +726,7 @@ int locate_msssim_pairs(const int8_t* a, const int32_t* aflags, const int8_t* b,
 /* ---- differentiable augmentation of an image batch and its adjoint (csrc/diffaug.hip; locate_amd/augment.py; the definition in
  *      float64 numpy: tests/helpers/diffaug_model.py).  x, y fp32 [n, 3, S, S] contiguous, 4-byte aligned (16-byte stores and loads
  *      where a buffer allows them; the values do not depend on it), S in {32, 64, 128, 256}, n <= 65535; params fp32 [n, 12], one row
- *      per image: b, s, c, ty, tx, y0, y1, x0, x1, 0, 0, 0 (the integers exact in fp32).  policy: bit 0 colour, bit 1 translation,
+ *      per image: b, s, c, ty, tx, y0, y1, x0, x1, mask, 0, 0 (the integers exact in fp32; mask 0: every op of the policy runs - below).  policy: bit 0 colour, bit 1 translation,
  *      bit 2 cutout - it selects the kernel, and an op that is off reads none of its words and executes none of its arithmetic.
  *      Forward: z = c (s (x - mu) + mu - M) + M + b with mu the mean over the three channels of a pixel and M the image's mean; w the
  *      gather z[c, i - ty, j - tx], exactly 0.0 outside the frame; y = keep * w, keep = 0.0f on [y0, y1) x [x0, x1) and 1.0f elsewhere,
@@ -739,6 +739,22 @@ int locate_diffaug_param_floats(void);
 size_t locate_diffaug_workspace_bytes(int n, int S);
 int locate_diffaug_fwd(const float* x, const float* params, float* y, int n, int S, int policy, void* workspace, void* stream);
 int locate_diffaug_bwd(const float* gy, const float* params, float* gx, int n, int S, int policy, void* workspace, void* stream);
+
+/* ---- adaptive augmentation beside the training step (csrc/ada.hip; locate_amd/augment.py, AdaptiveDiffAugment; the definition in
+ *      numpy, which both entries equal with ==: tests/helpers/ada_model.py).  Word 9 of a diffaug parameter row is a per-image op
+ *      mask, a small exact integer in fp32: bit k set switches op k off for that image, and the image's result is then, bit for bit,
+ *      that of the policy without those bits.  state: a record of 16 32-bit words at a fixed device address - 0 p (fp32), 1 r of the
+ *      last closed window (fp32), 2 window sum, 3 logits counted in the window, 4 observations in the window, 5 windows closed, 6 ups,
+ *      7 downs, 8 NaN logits seen, 9 ring rows written, 10 .. 15 zero.
+ *      gate: raw_rows fp32 [n, 12] hold words 0 .. 8 of a row and, in words 9 .. 11, a uniform g_k in [0, 1) per op; out_rows gets
+ *      words 0 .. 8 bit for bit, the mask in word 9 (bit k set where op k is in `policy` and not g_k < p, p = state word 0) and zeros.
+ *      observe: adds #(x > 0) - #(x < 0) and the count of the non-NaN ones of the B logits to the window; the interval-th
+ *      observation closes it: r = (float)((double)sum / (double)counted), p = min(max(p +- step, 0), p_max) for r > / < target (one
+ *      fp32 addition), {iteration, r, p, counted} into ring row (rows written) % capacity (4 words a row).  One block, integer sums:
+ *      order-free.  No allocation, no host read, no atomics: legal under stream capture. ---- */
+int locate_ada_gate(const float* raw_rows, const void* state, float* out_rows, int n, int policy, void* stream);
+int locate_ada_observe(const float* d_true, int B, int iteration, void* state, void* ring, int capacity, int interval, float target, float step,
+                       float p_max, void* stream);
 
 #ifdef __cplusplus
 }

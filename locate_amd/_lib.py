@@ -206,6 +206,8 @@ PROTOTYPES = {
     "locate_diffaug_workspace_bytes": (c_sz, [c_i, c_i]),
     "locate_diffaug_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
     "locate_diffaug_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
+    "locate_ada_gate": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
+    "locate_ada_observe": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_p]),
 }
 
 
@@ -215,7 +217,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 22
+EXPECTED_ABI = 23
 
 
 _lib = None

@@ -186,7 +186,13 @@ class DiffAugment:
         rows = np.ascontiguousarray(rows, dtype=np.float32)
         if rows.shape != (4 * self.batch, PARAM_FLOATS):
             raise ValueError("rows must be [%d, %d], got %s" % (4 * self.batch, PARAM_FLOATS, rows.shape))
-        dev = self.params
+        self._stage(rows, self.params)
+        self.draws += 1
+        self.last_rows = rows
+        return rows
+
+    def _stage(self, rows, dev):
+        """rows -> the device tensor `dev` through the next pinned slot, on the current stream"""
         slot = self._slot
         self._slot = (slot + 1) % self.SLOTS
         if self._events[slot] is not None:
@@ -195,9 +201,6 @@ class DiffAugment:
         dev.copy_(self._pinned[slot], non_blocking=True)
         self._events[slot] = torch.cuda.Event()
         self._events[slot].record()
-        self.draws += 1
-        self.last_rows = rows
-        return rows
 
     def _rows(self, first, n):
         if self.draws == 0:
@@ -232,7 +235,197 @@ class DiffAugment:
                 "draws": int(self.draws)}
 
     def load_state_dict(self, state):
+        if state.get("adaptive"):
+            raise ValueError("the saved augmentation is an AdaptiveDiffAugment's (it carries p and the gate's stream); this run's is a "
+                             "plain DiffAugment: resume with the same --ada-target settings")
+        self._load_stream(state)
+
+    def _load_stream(self, state):
         if (state["policy"], int(state["S"]), int(state["batch"])) != (self.policy, self.S, self.batch):
             raise ValueError("the saved augmentation is %r at S = %d, batch %d; this run's is %r at S = %d, batch %d"
                              % (state["policy"], int(state["S"]), int(state["batch"]), self.policy, self.S, self.batch))
         self.generator.set_state(state["generator_state"])
+
+
+# ---- adaptive augmentation ----------------------------------------------------------------------------------------------------------
+ADA_STATE_WORDS = 16
+ADA_RING_WORDS = 4          # {iteration, r, p, logits counted in the closed window}
+# words 0 .. 9 of the device record (csrc/ada.hip; the layout is defined in tests/helpers/ada_model.py, FIELDS)
+ADA_FIELDS = ("p", "r", "sum", "counted", "seen", "closed", "ups", "downs", "nan", "rows")
+GATE_WORD = 9
+_GATE_CAP = np.nextafter(np.float32(1.0), np.float32(0.0))          # the largest fp32 below 1
+
+
+def ada_step(batch, interval, kimg):
+    """What p moves by per closed window, batch * interval / (kimg * 1000): float64, rounded once to fp32 (kimg = inf: 0)."""
+    return np.float32(float(batch) * float(interval) / (float(kimg) * 1000.0))
+
+
+class AdaptiveDiffAugment(DiffAugment):
+    """DiffAugment whose strength steers itself (adaptive discriminator augmentation; Karras et al. 2020, "Training Generative
+    Adversarial Networks with Limited Data"): every op of the policy is applied to every image independently with probability p, and
+    p follows the overfitting indicator
+
+        r_t = E[sign(D(real))]          over the last `interval` batches: near 0 for a healthy discriminator, near 1 for one that
+                                        has learned the training set by heart;
+        p  <-  min(max(p +- step, 0), p_max)   for r_t > / < target,    step = batch * interval / (kimg * 1000)
+
+    (p would take kimg thousand images to go from 0 to 1).  All of it runs on the device BESIDE the step, with no host read:
+    observe(d_true) is one single-block launch that adds the signs of the B logits to a window kept in a 64-byte device record and,
+    every interval-th call, closes the window, moves p and appends {iteration, r_t, p} to a device ring; draw() uploads the raw rows
+    - the DiffAugment rows of the same seed, words 0 .. 8 unchanged, plus three uniforms per row from a SECOND generator - to a
+    staging tensor and launches a gate kernel that writes `params`: op k of an image is applied iff its uniform is < p (strictly),
+    and is otherwise switched off in the row's mask word, which the diffaug kernels honour bit for bit.  So a new p takes effect at
+    the next draw(), never inside an iteration, and a replayed hipGraph, which reads `params` at its fixed address, needs no change.
+    TrainLoop.iteration and Trainer call draw() and observe() themselves.  Construction needs no GPU.
+
+    Two corners:  kimg=float("inf"), initial_p=1.0 is fixed-strength DiffAugment with the r_t curve recorded - any augmented run
+    gets the indicator;  initial_p=0.0 with r_t below target stays at p = 0, where T is a copy and the run equals the run without
+    an augment, bit for bit.
+
+    status() is one 64-byte copy; flush() one copy of the ring rows since the last flush; curve() the flushed rows.  state_dict()
+    carries both generators, the device record (one small host read), the flushed curve and the settings: a resumed run continues
+    p, the open window and both streams.  A rollback (snapshot.py) rewinds none of them, like the input pipeline's.  Under data
+    parallelism each rank would steer its own p from its own shard: out of scope, and refused by TrainLoop and Trainer."""
+
+    def __init__(self, S, batch, policy="color,translation,cutout", seed=999, device="cuda:0", target=0.6, interval=4, kimg=500.0,
+                 initial_p=0.0, p_max=1.0, capacity=4096):
+        super().__init__(S, batch, policy=policy, seed=seed, device=device)
+        self.target, self.interval, self.kimg = float(target), int(interval), float(kimg)
+        self.p_max, self.initial_p, self.capacity = float(p_max), float(initial_p) + 0.0, int(capacity)
+        if not np.isfinite(self.target):
+            raise ValueError("target must be a finite number, got %r" % (target,))
+        if self.interval < 1 or self.batch * self.interval >= 1 << 31:
+            raise ValueError("interval must be >= 1 with batch * interval < 2^31, got %r" % (interval,))
+        if not self.kimg > 0:
+            raise ValueError("kimg must be > 0 (float('inf'): p never moves), got %r" % (kimg,))
+        if not 0.0 < self.p_max <= 1.0:
+            raise ValueError("p_max must be in (0, 1], got %r" % (p_max,))
+        if not 0.0 <= self.initial_p <= self.p_max:
+            raise ValueError("initial_p must be in [0, p_max], got %r" % (initial_p,))
+        if self.capacity < 1:
+            raise ValueError("capacity must be >= 1, got %r" % (capacity,))
+        self.step = ada_step(self.batch, self.interval, self.kimg)
+        self.gate_generator = torch.Generator().manual_seed(int(seed) + 0xADA)
+        self.observations = 0          # observe() calls in all, across resumes: the default iteration label
+        self._record = np.zeros(ADA_STATE_WORDS, np.uint32)          # what the device record starts from, until it exists
+        self._record[0] = np.array([self.initial_p], np.float32).view(np.uint32)[0]
+        self._state = self._ring = self._raw = None
+        self._window_seen, self._ring_rows, self._flushed = 0, 0, 0          # the host's mirror of words 4 and 9, and the rows already flushed
+        self._curve = np.zeros((0, ADA_RING_WORDS), np.uint32)
+
+    # ---- device tensors, made on first use -----------------------------------------------------------------------------------------
+    @property
+    def state(self):
+        """the 64-byte device record (int32 [16])"""
+        if self._state is None:
+            self._state = torch.from_numpy(self._record.view(np.int32).copy()).to(self.device)
+            self._ring = torch.zeros(self.capacity, ADA_RING_WORDS, dtype=torch.int32, device=self.device)
+            self._raw = torch.zeros(4 * self.batch, PARAM_FLOATS, dtype=torch.float32, device=self.device)
+        return self._state
+
+    def draw(self):
+        """The next iteration's 4B rows: DiffAugment's draw of the same seed, and in words 9 .. 11 three gate uniforms per row from
+        the second generator (one float64 rand(rows, 3), rounded to fp32 and capped at the largest fp32 below 1); gated on the
+        device with the p of this moment.  Returns the raw host rows."""
+        rows = draw_parameters(4 * self.batch, self.S, self.generator, self.bits)
+        g = torch.rand(4 * self.batch, 3, generator=self.gate_generator, dtype=torch.float64).numpy()
+        rows[:, GATE_WORD:GATE_WORD + 3] = np.minimum(g.astype(np.float32), _GATE_CAP)
+        return self.upload(rows)
+
+    def upload(self, rows):
+        """Hand-made RAW rows (numpy float32 [4B, 12], uniforms in words 9 .. 11) in place of a draw."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if rows.shape != (4 * self.batch, PARAM_FLOATS):
+            raise ValueError("rows must be [%d, %d], got %s" % (4 * self.batch, PARAM_FLOATS, rows.shape))
+        out, state = self.params, self.state
+        self._stage(rows, self._raw)
+        check(lib().locate_ada_gate(self._raw.data_ptr(), state.data_ptr(), out.data_ptr(), 4 * self.batch, self.bits, _stream()),
+              "locate_ada_gate")
+        self.draws += 1
+        self.last_rows = rows
+        return rows
+
+    def observe(self, d_true, iteration=None):
+        """One launch on the current stream: D's logits on this iteration's real batch (the step's out["d_true"]) into the window.
+        `iteration` labels the ring row if this observation closes a window (default: the count of observations so far)."""
+        if not (torch.is_tensor(d_true) and d_true.is_cuda and d_true.dtype == torch.float32 and d_true.is_contiguous() and d_true.numel() > 0):
+            raise TypeError("observe takes a contiguous, non-empty fp32 tensor of logits on the GPU")
+        state = self.state
+        self.observations += 1
+        label = self.observations if iteration is None else int(iteration)
+        check(lib().locate_ada_observe(d_true.data_ptr(), d_true.numel(), label, state.data_ptr(), self._ring.data_ptr(), self.capacity,
+                                       self.interval, self.target, float(self.step), self.p_max, _stream()), "locate_ada_observe")
+        self._window_seen += 1
+        if self._window_seen >= self.interval:          # what the kernel does to words 4 and 9
+            self._window_seen = 0
+            self._ring_rows += 1
+
+    # ---- reading ---------------------------------------------------------------------------------------------------------------------
+    def _read_record(self):
+        if self._state is None:
+            return self._record.copy()
+        return self._state.cpu().numpy().view(np.uint32).copy()
+
+    def status(self):
+        """{"p", "r_t", "updates", "ups", "downs", "nonfinite"}: one 64-byte copy from the device"""
+        w = self._read_record()
+        return {"p": float(w[0:1].view(np.float32)[0]), "r_t": float(w[1:2].view(np.float32)[0]), "updates": int(w[5]), "ups": int(w[6]),
+                "downs": int(w[7]), "nonfinite": int(w[8])}
+
+    def flush(self):
+        """The ring rows appended since the last flush (one copy from the device) join curve(); returns them as curve() would.  Rows
+        that the ring has overwritten since - more than `capacity` windows between two flushes - are lost."""
+        first, last = max(self._flushed, self._ring_rows - self.capacity), self._ring_rows
+        self._flushed = last
+        if last == first:
+            return []
+        a, b = first % self.capacity, (last - 1) % self.capacity + 1
+        if a < b:
+            rows = self._ring[a:b].cpu().numpy()
+        else:          # the span wraps: the whole ring in one copy
+            ring = self._ring.cpu().numpy()
+            rows = np.concatenate([ring[a:], ring[:b]])
+        rows = rows.view(np.uint32)
+        self._curve = np.concatenate([self._curve, rows])
+        return _curve_records(rows)
+
+    def curve(self):
+        """every flushed row: [{"iteration", "r_t", "p"}]"""
+        return _curve_records(self._curve)
+
+    # ---- state -----------------------------------------------------------------------------------------------------------------------
+    def _settings(self):
+        return {"target": self.target, "interval": self.interval, "kimg": self.kimg, "p_max": self.p_max, "capacity": self.capacity}
+
+    def state_dict(self):
+        self.flush()
+        state = super().state_dict()
+        state.update({"adaptive": True, "gate_generator_state": self.gate_generator.get_state(),
+                      "record": torch.from_numpy(self._read_record().view(np.int32).copy()), "observations": int(self.observations),
+                      "curve": torch.from_numpy(self._curve.view(np.int32).copy()), "settings": self._settings()})
+        return state
+
+    def load_state_dict(self, state):
+        if not state.get("adaptive"):
+            raise ValueError("the saved augmentation is a plain DiffAugment's (no p, no gate stream); this run's is an "
+                             "AdaptiveDiffAugment: resume without --ada-target")
+        saved = {k: state["settings"][k] for k in ("target", "interval", "kimg", "p_max")}
+        mine = {k: v for k, v in self._settings().items() if k in saved}
+        if saved != mine:
+            raise ValueError("the saved adaptive augmentation ran with %r, this run's has %r" % (saved, mine))
+        self._load_stream(state)
+        self.gate_generator.set_state(state["gate_generator_state"])
+        self._record = state["record"].numpy().view(np.uint32).copy()
+        self.observations = int(state["observations"])
+        self._curve = state["curve"].numpy().view(np.uint32).reshape(-1, ADA_RING_WORDS).copy()
+        self._window_seen, self._ring_rows = int(self._record[4]), int(self._record[9])
+        self._flushed = self._ring_rows          # the ring itself is not carried: its flushed rows are in the curve
+        if self._state is not None:
+            self._state.copy_(torch.from_numpy(self._record.view(np.int32).copy()))
+
+
+def _curve_records(rows):
+    rows = np.ascontiguousarray(rows, np.uint32).reshape(-1, ADA_RING_WORDS)
+    it, r, p = rows[:, 0].copy().view(np.int32), rows[:, 1].copy().view(np.float32), rows[:, 2].copy().view(np.float32)
+    return [{"iteration": int(it[k]), "r_t": float(r[k]), "p": float(p[k])} for k in range(len(rows))]

@@ -2,7 +2,7 @@
 // numpy: tests/helpers/diffaug_model.py).  Every image the discriminator sees passes through one random transform T - colour, then
 // translation, then cutout - whose parameters arrive as a row of DA_PARAMS fp32 words per image, drawn on the host:
 //   word 0 b, 1 s, 2 c (brightness offset, saturation and contrast factors), 3 ty, 4 tx (shift), 5 y0, 6 y1, 7 x0, 8 x1 (cut
-//   rectangle [y0, y1) x [x0, x1)); the integers are small exact integers stored as fp32; words 9 .. 11 are zero.
+//   rectangle [y0, y1) x [x0, x1)); the integers are small exact integers stored as fp32; word 9 is the per-image op mask (below; 0: every op of the policy runs); words 10 and 11 are zero.
 // Forward, per image x [3, S, S] with mu[p] = mean_c x[c, p] and M = mean(x):
 //   z[c, p] = c (s (x[c, p] - mu[p]) + mu[p] - M) + M + b,   w[c, i, j] = z[c, i - ty, j - tx] inside the frame and exactly 0.0
 //   elsewhere (a gather, nothing is multiplied),   y = keep * w with keep = 0.0f inside the rectangle and 1.0f outside (an fp32
@@ -24,13 +24,24 @@
 // element belongs to the same thread whatever the buffer's alignment, so an image's output depends on that image and its row
 // alone.  Every other operation is one IEEE fp32 operation spelled out below under `fp contract(off)`, with fmaf where a fused
 // multiply-add is meant.
+//
+// PER-IMAGE OP MASK (adaptive augmentation, csrc/ada.hip).  Word 9 of a row is a small exact integer: bit k set switches op k off
+// for THIS image; 0 is the behaviour above.  The ops that run are OPS = POLICY & ~mask, and every kernel below branches once per
+// block on OPS into the body instantiated for exactly that subset, so an image's output under policy P and mask m is, bit for bit,
+// what the instantiation P & ~m writes for the same row: a masked op executes none of its arithmetic (no colour chain, ty = tx = 0,
+// no multiplication by keep).  The mask is the same in every thread of a block (blockIdx.x / blockIdx.y names the image): the branch
+// is wave-uniform.  The image loads of the one-launch form and of launch 1 are issued BEFORE the branch, so that an unmasked image
+// waits for nothing it did not wait for before.  OPS == 0 is a plain copy: no LDS, no reduction, 16-byte loads and stores where each
+// side allows them.  At S >= 128 launch 1 leaves an image whose colour is masked as soon as the mask has arrived - it adds nothing
+// and writes no partial - and launch 2 then reads none.
 #include "multitensor.h"
 
 #define DA_PARAMS 12
 #define DA_COLOR 1
 #define DA_TRANSLATION 2
 #define DA_CUTOUT 4
-#define DA_SMALL_MAX 64          // largest S of the one-launch form
+#define DA_MASK_WORD 9          // bit k set: op k is off for this image
+#define DA_SMALL_MAX 64         // largest S of the one-launch form
 
 struct DaSum {
     double s;
@@ -54,6 +65,38 @@ __device__ __forceinline__ DaRow da_row(const float* __restrict__ params, int im
     if (POLICY & DA_CUTOUT) { r.y0 = (int)p[5]; r.y1 = (int)p[6]; r.x0 = (int)p[7]; r.x1 = (int)p[8]; }
     return r;
 }
+
+// The ops that run for image `img`: the static policy without the bits of the row's mask word; the same value in every lane (the
+// word's address is the block's, so it arrives in a scalar register, which the "s" operand below insists on).  In two steps, so
+// that a kernel can ask for the word first, issue its image loads, and only then wait for the word.
+__device__ __forceinline__ float da_mask_word(const float* __restrict__ params, int img) {
+    return params[(size_t)img * DA_PARAMS + DA_MASK_WORD];
+}
+
+template <int POLICY>
+__device__ __forceinline__ int da_ops(float mask_word) {
+    // The empty statement pins the conversion, and with it the wait for the word, where this call stands: left to itself the
+    // compiler lifts both to the top of the kernel, in front of the image loads.
+    unsigned bits = __float_as_uint(mask_word);
+    asm volatile("" : "+s"(bits));
+    const float word = __uint_as_float(bits);
+    return POLICY & ~(int)word;
+}
+
+// `ops` is a subset of POLICY: run BODY with the compile-time constant OPS equal to it (1 .. 7; 0 is the callers' copy path)
+#define DA_CASE(POLICY, K, BODY)                   \
+    case K:                                        \
+        if constexpr (((POLICY) & (K)) == (K)) {   \
+            constexpr int OPS = K;                 \
+            BODY;                                  \
+        }                                          \
+        break;
+#define DA_DISPATCH(POLICY, ops, BODY)                                                                              \
+    switch (ops) {                                                                                                  \
+        DA_CASE(POLICY, 1, BODY) DA_CASE(POLICY, 2, BODY) DA_CASE(POLICY, 3, BODY) DA_CASE(POLICY, 4, BODY)         \
+        DA_CASE(POLICY, 5, BODY) DA_CASE(POLICY, 6, BODY) DA_CASE(POLICY, 7, BODY)                                  \
+        default: break;                                                                                             \
+    }
 
 __device__ __forceinline__ float da_keep(const DaRow& r, int i, int j) {
     return (i >= r.y0 && i < r.y1 && j >= r.x0 && j < r.x1) ? 0.0f : 1.0f;
@@ -165,7 +208,54 @@ __device__ __forceinline__ void da_quad(const float* src, float* dst, bool dst_v
 
 __device__ __forceinline__ float da_mean(double total, int S) { return (float)(total / (double)(3 * S * S)); }
 
+// ---- an image without an op: a plain copy ----------------------------------------------------------------------------------------------
+// one 16-byte word (four neighbouring elements), by a 16-byte access where that side allows it
+__device__ __forceinline__ float4 da_load4(const float* p, bool vec) {
+    if (vec) return *reinterpret_cast<const float4*>(p);
+    float4 v;
+    v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3];
+    return v;
+}
+
+__device__ __forceinline__ void da_store4(float* p, bool vec, const float4& v) {
+    if (vec) {
+        *reinterpret_cast<float4*>(p) = v;
+    } else {
+        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
+    }
+}
+
 // ---- S <= 64: a block per image, the image in LDS --------------------------------------------------------------------------------------
+// what follows the staging for the ops OPS (not 0): the reduction, if colour runs, and the apply
+template <int OPS, bool BWD>
+__device__ __forceinline__ void da_small_apply(const float* __restrict__ params, const float* img, float* dst, bool dst_vec, int S, DaSum acc,
+                                               DaSum* red, float* mean_sh) {
+    const DaRow r = da_row<OPS>(params, blockIdx.x);
+    const int quads_per_row = S >> 2, n_quads = S * quads_per_row;
+    DaColour k = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (OPS & DA_COLOR) {
+        if (BWD) {          // mean(gz): the masked, shifted gradient, in the order of the output's pixel quads
+            for (int q = threadIdx.x; q < n_quads; q += MT_THREADS) {
+                const int i = q / quads_per_row, j = (q - i * quads_per_row) << 2;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    float a0, a1, a2;
+                    da_pixel<OPS, true, false>(img, S, r, k, i, j + u, a0, a1, a2);
+                    acc.s = ((acc.s + (double)a0) + (double)a1) + (double)a2;
+                }
+            }
+        }
+        const DaSum total = mt_block_total(acc, red);
+        if (threadIdx.x == 0) *mean_sh = da_mean(total.s, S);
+        __syncthreads();
+        k = BWD ? da_colour_bwd(r, *mean_sh) : da_colour_fwd(r, *mean_sh);
+    }
+    for (int q = threadIdx.x; q < n_quads; q += MT_THREADS) {
+        const int i = q / quads_per_row, j = (q - i * quads_per_row) << 2;
+        da_quad<OPS, BWD>(img, dst, dst_vec, S, r, k, i, j);
+    }
+}
+
 template <int POLICY, bool BWD>
 __global__ void __launch_bounds__(MT_THREADS) diffaug_small_kernel(const float* __restrict__ in, const float* __restrict__ params,
                                                                     float* __restrict__ out, int S) {
@@ -176,74 +266,73 @@ __global__ void __launch_bounds__(MT_THREADS) diffaug_small_kernel(const float* 
     const int n_el = 3 * S * S, n4 = n_el >> 2;          // S is a multiple of 4
     const float* src = in + (size_t)blockIdx.x * n_el;
     float* dst = out + (size_t)blockIdx.x * n_el;
-    const DaRow r = da_row<POLICY>(params, blockIdx.x);
     const bool src_vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0, dst_vec = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    const float mask_word = da_mask_word(params, blockIdx.x);
 
-    // stage: 16-byte word w of the image belongs to thread w % 256 whatever the alignment
+    // stage: 16-byte word w of the image belongs to thread w % 256 whatever the alignment.  The first round's loads are issued
+    // BEFORE the mask word is looked at (its wait would otherwise stand in front of them: +0.5 us at 192 x 3 x 64 x 64,
+    // profiles/notes_ada.md); what is done with the loaded words depends on it: an image without an op goes straight to dst.  The
+    // forward's sum is taken under the STATIC policy (a masked colour leaves it unused: da_small_apply<OPS> never looks at it).
     DaSum acc = {0.0};
+    int ops;
     if (src_vec) {
+        float4 v[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int w = u * MT_THREADS + threadIdx.x;
+            if (w < n4) v[u] = reinterpret_cast<const float4*>(src)[w];
+        }
+        ops = da_ops<POLICY>(mask_word);
         for (int w0 = 0; w0 < n4; w0 += 4 * MT_THREADS) {
-            float4 v[4];
+            if (w0 > 0) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int w = w0 + u * MT_THREADS + threadIdx.x;
-                if (w < n4) v[u] = reinterpret_cast<const float4*>(src)[w];
+                for (int u = 0; u < 4; ++u) {
+                    const int w = w0 + u * MT_THREADS + threadIdx.x;
+                    if (w < n4) v[u] = reinterpret_cast<const float4*>(src)[w];
+                }
             }
+            if (ops == 0) {
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int w = w0 + u * MT_THREADS + threadIdx.x;
-                if (w < n4) {
-                    img4[w] = v[u];
-                    if ((POLICY & DA_COLOR) && !BWD) acc.s = (((acc.s + (double)v[u].x) + (double)v[u].y) + (double)v[u].z) + (double)v[u].w;
+                for (int u = 0; u < 4; ++u) {
+                    const int w = w0 + u * MT_THREADS + threadIdx.x;
+                    if (w < n4) da_store4(dst + 4 * w, dst_vec, v[u]);
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int w = w0 + u * MT_THREADS + threadIdx.x;
+                    if (w < n4) {
+                        img4[w] = v[u];
+                        if ((POLICY & DA_COLOR) && !BWD) acc.s = (((acc.s + (double)v[u].x) + (double)v[u].y) + (double)v[u].z) + (double)v[u].w;
+                    }
                 }
             }
         }
     } else {
+        ops = da_ops<POLICY>(mask_word);
         for (int w = threadIdx.x; w < n4; w += MT_THREADS) {
             float4 v;
             v.x = src[4 * w]; v.y = src[4 * w + 1]; v.z = src[4 * w + 2]; v.w = src[4 * w + 3];
-            img4[w] = v;
-            if ((POLICY & DA_COLOR) && !BWD) acc.s = (((acc.s + (double)v.x) + (double)v.y) + (double)v.z) + (double)v.w;
-        }
-    }
-    __syncthreads();
-
-    const int quads_per_row = S >> 2, n_quads = S * quads_per_row;
-    DaColour k = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (POLICY & DA_COLOR) {
-        if (BWD) {          // mean(gz): the masked, shifted gradient, in the order of the output's pixel quads
-            for (int q = threadIdx.x; q < n_quads; q += MT_THREADS) {
-                const int i = q / quads_per_row, j = (q - i * quads_per_row) << 2;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    float a0, a1, a2;
-                    da_pixel<POLICY, true, false>(img, S, r, k, i, j + u, a0, a1, a2);
-                    acc.s = ((acc.s + (double)a0) + (double)a1) + (double)a2;
-                }
+            if (ops == 0) {
+                da_store4(dst + 4 * w, dst_vec, v);
+            } else {
+                img4[w] = v;
+                if ((POLICY & DA_COLOR) && !BWD) acc.s = (((acc.s + (double)v.x) + (double)v.y) + (double)v.z) + (double)v.w;
             }
         }
-        const DaSum total = mt_block_total(acc, red);
-        if (threadIdx.x == 0) mean_sh = da_mean(total.s, S);
-        __syncthreads();
-        k = BWD ? da_colour_bwd(r, mean_sh) : da_colour_fwd(r, mean_sh);
     }
-    for (int q = threadIdx.x; q < n_quads; q += MT_THREADS) {
-        const int i = q / quads_per_row, j = (q - i * quads_per_row) << 2;
-        da_quad<POLICY, BWD>(img, dst, dst_vec, S, r, k, i, j);
-    }
+    if (ops == 0) return;          // the whole block: `ops` is the image's
+    __syncthreads();
+    DA_DISPATCH(POLICY, ops, (da_small_apply<OPS, BWD>(params, img, dst, dst_vec, S, acc, red, &mean_sh)))
 }
 
 // ---- S >= 128, launch 1: a float64 partial per (image, slab) ---------------------------------------------------------------------------
-template <int POLICY, bool BWD>
-__global__ void __launch_bounds__(MT_THREADS) diffaug_partial_kernel(const float* __restrict__ in, const float* __restrict__ params,
-                                                                      double* __restrict__ partials, int S) {
-    __shared__ DaSum red[MT_WAVES];
+template <int OPS, bool BWD>
+__device__ __forceinline__ void da_partial(const float* __restrict__ params, const float4 (&v)[MT_PER_THREAD], double* __restrict__ partials,
+                                           int S, DaSum* red) {
     const int n_el = 3 * S * S, slabs = n_el / MT_CHUNK;          // S >= 128: a whole number of slabs
     const int slab = blockIdx.x, image = blockIdx.y;
-    const float* src = in + (size_t)image * n_el + (size_t)slab * MT_CHUNK;
-    const DaRow r = da_row<POLICY>(params, image);
-    float4 v[MT_PER_THREAD];
-    mt_read_lanes(src, MT_CHUNK, v);
+    const DaRow r = da_row<OPS>(params, image);
     DaSum acc = {0.0};
 #pragma unroll
     for (int u = 0; u < MT_PER_THREAD; ++u) {
@@ -254,7 +343,7 @@ __global__ void __launch_bounds__(MT_THREADS) diffaug_partial_kernel(const float
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const bool lands = (unsigned)(si - r.ty) < (unsigned)S && (unsigned)(sj + t - r.tx) < (unsigned)S;
-                if (POLICY & DA_CUTOUT) e[t] = da_mul(da_keep(r, si, sj + t), e[t]);
+                if (OPS & DA_CUTOUT) e[t] = da_mul(da_keep(r, si, sj + t), e[t]);
                 e[t] = lands ? e[t] : 0.0f;
             }
         }
@@ -264,26 +353,58 @@ __global__ void __launch_bounds__(MT_THREADS) diffaug_partial_kernel(const float
     if (threadIdx.x == 0) partials[(size_t)image * slabs + slab] = total.s;
 }
 
-// ---- S >= 128, launch 2: the image streamed; a thread per pixel quad ------------------------------------------------------------------
 template <int POLICY, bool BWD>
-__global__ void __launch_bounds__(MT_THREADS) diffaug_apply_kernel(const float* __restrict__ in, const float* __restrict__ params,
-                                                                    float* __restrict__ out, const double* __restrict__ partials, int S) {
-    const int n_el = 3 * S * S, slabs = n_el / MT_CHUNK, image = blockIdx.y;
-    const float* src = in + (size_t)image * n_el;
-    float* dst = out + (size_t)image * n_el;
-    const bool dst_vec = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
-    const DaRow r = da_row<POLICY>(params, image);
+__global__ void __launch_bounds__(MT_THREADS) diffaug_partial_kernel(const float* __restrict__ in, const float* __restrict__ params,
+                                                                      double* __restrict__ partials, int S) {
+    __shared__ DaSum red[MT_WAVES];
+    const int n_el = 3 * S * S;
+    const int slab = blockIdx.x, image = blockIdx.y;
+    const float* src = in + (size_t)image * n_el + (size_t)slab * MT_CHUNK;
+    const float mask_word = da_mask_word(params, image);
+    float4 v[MT_PER_THREAD];
+    mt_read_lanes(src, MT_CHUNK, v);          // issued before the mask word is looked at: its wait does not stand in front of them
+    const int ops = da_ops<POLICY>(mask_word);
+    if (!(ops & DA_COLOR)) return;          // colour is masked for this image: no partial is written, and launch 2 reads none
+    DA_DISPATCH(POLICY, ops, (da_partial<OPS, BWD>(params, v, partials, S, red)))
+}
+
+// ---- S >= 128, launch 2: the image streamed; a thread per pixel quad ------------------------------------------------------------------
+template <int OPS, bool BWD>
+__device__ __forceinline__ void da_apply(const float* src, const float* __restrict__ params, float* dst, bool dst_vec,
+                                         const double* __restrict__ partials, int S, int image, int i, int j) {
+    const int slabs = 3 * S * S / MT_CHUNK;
+    const DaRow r = da_row<OPS>(params, image);
     DaColour k = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (POLICY & DA_COLOR) {
+    if (OPS & DA_COLOR) {
         double total = 0.0;
         for (int s = 0; s < slabs; ++s) total += partials[(size_t)image * slabs + s];          // ascending, the same in every thread
         const float mean = da_mean(total, S);
         k = BWD ? da_colour_bwd(r, mean) : da_colour_fwd(r, mean);
     }
+    da_quad<OPS, BWD>(src, dst, dst_vec, S, r, k, i, j);
+}
+
+template <int POLICY, bool BWD>
+__global__ void __launch_bounds__(MT_THREADS) diffaug_apply_kernel(const float* __restrict__ in, const float* __restrict__ params,
+                                                                    float* __restrict__ out, const double* __restrict__ partials, int S) {
+    const int n_el = 3 * S * S, image = blockIdx.y;
+    const float* src = in + (size_t)image * n_el;
+    float* dst = out + (size_t)image * n_el;
+    const bool src_vec = (reinterpret_cast<uintptr_t>(src) & 15) == 0, dst_vec = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
+    const int ops = da_ops<POLICY>(da_mask_word(params, image));
     const int quads_per_row = S >> 2, q = blockIdx.x * MT_THREADS + threadIdx.x;
     if (q >= S * quads_per_row) return;
     const int i = q / quads_per_row, j = (q - i * quads_per_row) << 2;
-    da_quad<POLICY, BWD>(src, dst, dst_vec, S, r, k, i, j);
+    if (ops == 0) {          // the quad of each plane, copied
+        const int o = i * S + j, plane = S * S;
+        float4 v[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = da_load4(src + o + c * plane, src_vec);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) da_store4(dst + o + c * plane, dst_vec, v[c]);
+        return;
+    }
+    DA_DISPATCH(POLICY, ops, (da_apply<OPS, BWD>(src, params, dst, dst_vec, partials, S, image, i, j)))
 }
 
 // ---- host entries ---------------------------------------------------------------------------------------------------------------------

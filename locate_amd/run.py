@@ -9,6 +9,8 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--rollback-every 0] [--max-rollbacks 3] [--spill-every 0] [--neighbours 0] [--neighbours-k 3]
                              [--manifold 0] [--manifold-k 3] [--spectrum-images 0] [--spectrum-window none]
                              [--msssim-pairs 0] [--modes 0] [--modes-bins 128] [--modes-images 16384]
+                             [--diffaugment POLICY] [--ada-target X] [--ada-kimg 500] [--ada-interval 4] [--ada-initial-p 0]
+                             [--ada-p-max 1]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -76,7 +78,15 @@ Differences from the reference, all additions:
     domain, the samples are assigned to the cells and every cell's share is tested against the real images', with a real-against-
     real baseline: a record in `OUT/error/modes.json` and the picture `OUT/{epoch}-modes.png` of the cells' centres, the most
     under-represented first.  It names the modes that are missing.  The evaluation has no side effect on the training; under
-    data parallelism only rank 0 evaluates."""
+    data parallelism only rank 0 evaluates;
+  * `--diffaugment POLICY` (off by default): every batch the discriminator sees passes through the differentiable augmentation of
+    `locate_amd.augment`; `--ada-target X` beside it (off by default: the policy at full strength) makes it adaptive - every op is
+    applied per image with a probability p that two launches beside the step steer from r_t = E[sign(D(real))] (`--ada-kimg`,
+    `--ada-interval`, `--ada-initial-p`, `--ada-p-max`).  The ring of {iteration, r_t, p} is flushed at the progress line, and
+    `OUT/error/ada.json` - {"curve": [{"iteration", "r_t", "p"}, ...], "p", "r_t", "updates", "ups", "downs", "nonfinite"}, the
+    curve of the whole run, resumes included - is written after every epoch and when `max_iterations` stops the run.
+    `OUT/trainer.torch` and the spill's host state carry p, the open window and both random streams under "augment"; a state saved
+    with `--ada-target` is refused without it and the other way round.  Not under data parallelism."""
 import argparse
 import json
 import os
@@ -267,6 +277,7 @@ class Trainer:
         self.step, self.pipeline, self.out = step, pipeline, str(out)
         self.gen, self.dis = step.gen, step.dis
         self.augment = getattr(step, "augment", None)          # a DiffAugment: its rows are drawn before every iteration
+        self.adaptive = hasattr(self.augment, "observe")          # an AdaptiveDiffAugment: observed after every iteration
         self.batch = pipeline.batch
         self.epochs = None if epochs is None else int(epochs)
         self.max_iterations = None if max_iterations is None else int(max_iterations)
@@ -287,7 +298,7 @@ class Trainer:
                 raise ValueError("graphed=True replays whole iterations: miniter == 1 and diters == 1 throughout "
                                  "(miniter is %d in epoch %d, diters %d)" % (self.miniter_function(bad[0]) if bad else 1,
                                                                             bad[0] + 1 if bad else 1, self.diters))
-        self.loop = TrainLoop(step, 1, self.diters)
+        self.loop = TrainLoop(step, 1, self.diters)          # refuses an adaptive augment beside a data-parallel reducer
         self.device = next(self.gen.parameters()).device
         self._sampler_args = dict(fixed_noise=fixed_noise, images=images, seed=seed, **(sampler_options or {}))
         self._sampler = None
@@ -550,15 +561,20 @@ class Trainer:
             latent = torch.randn(latent_shape, device=self.device, generator=self._latent_gen)
             real, aug = self.pipeline.next_batch()
             self._runner = GraphedTrainStep(self.step, latent, real, aug)          # runs two real iterations on this batch
-            return self._runner.replay()
-        lat, real, aug = self._runner.inputs
-        lat.copy_(torch.randn(latent_shape, device=self.device, generator=self._latent_gen))
-        self.pipeline.next_batch(out_real=real, out_aug=aug)          # written straight into the graphs' static inputs
-        return self._runner.replay()
+        else:
+            lat, real, aug = self._runner.inputs
+            lat.copy_(torch.randn(latent_shape, device=self.device, generator=self._latent_gen))
+            self.pipeline.next_batch(out_real=real, out_aug=aug)          # written straight into the graphs' static inputs
+        out = self._runner.replay()
+        if self.adaptive:
+            self.augment.observe(out["d_true"])          # the replay's logits; the capture's two warm-up iterations are not observed
+        return out
 
     def _progress(self, e, sub, i, first, subepochs, batches, started):
         """first: the position this call of run() entered the sub-pass at (not 0 after a resume): the rate counts from there"""
         pairs = self.history.flush()          # the one host read of the losses
+        if self.adaptive:
+            self.augment.flush()          # the ring's new {iteration, r_t, p} rows, here where the loop reads from the device anyway
         before = self.rollbacks
         self._checks()
         if self.spill is not None and self.rollbacks == before and self.iterations - self._last_spill >= self.spill_every:
@@ -605,6 +621,12 @@ class Trainer:
             if also is not None:
                 records[-1].update(also())
         return _write_json(path, records), value
+
+    def _save_ada(self):
+        """out/error/ada.json: the adaptive augmentation's whole curve so far, {"iteration", "r_t", "p"} per closed window (counted
+        across resumes), and the counters of this moment"""
+        self.augment.flush()
+        return _write_json(os.path.join(self.out, "error", "ada.json"), dict(self.augment.status(), curve=self.augment.curve()))
 
     def _measure(self, e):
         """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
@@ -667,6 +689,8 @@ class Trainer:
                 while self.i < batches:
                     if self.max_iterations is not None and self.iterations >= self.max_iterations:
                         self._checks(before_save=True)
+                        if self.adaptive:
+                            self.written.append(self._save_ada())
                         self.written += self.save_state()
                         return self.iterations
                     followed = self.dynamics is not None and self.dynamics_every and (self.iterations + 1) % self.dynamics_every == 0
@@ -709,6 +733,8 @@ class Trainer:
                 self.formats.clear()
             if self._guards():
                 self.written.append(self._save_guards(e + 1))         # raises, before the save below, if a guard is exhausted
+            if self.adaptive:
+                self.written.append(self._save_ada())
             if self.swd is not None:
                 self.written.append(self._measure(e))
             if self.neighbours is not None:
@@ -802,6 +828,14 @@ def parser():
     ap.add_argument("--diffaugment", default="", metavar="POLICY",
                     help="differentiable augmentation of every batch the discriminator sees: a comma-separated subset of "
                          "color,translation,cutout (default: off)")
+    ap.add_argument("--ada-target", type=float, default=None, metavar="X",
+                    help="adaptive augmentation (needs --diffaugment): every op is applied per image with a probability p that rises "
+                         "while r_t = E[sign(D(real))] is above X and falls while below (the paper: 0.6); OUT/error/ada.json holds "
+                         "the r_t and p curves (default: off, --diffaugment at full strength)")
+    ap.add_argument("--ada-kimg", type=float, default=500.0, metavar="K", help="p takes K thousand images from 0 to 1; inf: p stays put")
+    ap.add_argument("--ada-interval", type=int, default=4, metavar="N", help="batches per window of r_t")
+    ap.add_argument("--ada-initial-p", type=float, default=0.0, metavar="P")
+    ap.add_argument("--ada-p-max", type=float, default=1.0, metavar="P")
     return ap
 
 
@@ -855,6 +889,19 @@ def main(argv=None):
             ap.error("--diffaugment: %s" % err)
         if args.image_size not in (32, 64, 128, 256):
             ap.error("--diffaugment takes --image-size 32, 64, 128 or 256")
+    if args.ada_target is not None:
+        if not diffaugment:
+            ap.error("--ada-target steers --diffaugment's strength: give a --diffaugment policy")
+        if not abs(args.ada_target) < float("inf"):
+            ap.error("--ada-target must be a finite number")
+        if not args.ada_kimg > 0:
+            ap.error("--ada-kimg must be > 0 (inf: p stays put)")
+        if args.ada_interval < 1:
+            ap.error("--ada-interval must be >= 1")
+        if not 0.0 < args.ada_p_max <= 1.0:
+            ap.error("--ada-p-max must be in (0, 1]")
+        if not 0.0 <= args.ada_initial_p <= args.ada_p_max:
+            ap.error("--ada-initial-p must be in [0, --ada-p-max]")
     guarded_step = args.clip_grad_norm is not None or args.no_skip_nonfinite
     if args.rollback_every > 0 and not (args.stats_every > 0 or guarded_step):
         ap.error("--rollback-every needs --stats-every or a guarded optimizer (--clip-grad-norm / --no-skip-nonfinite): "
@@ -877,8 +924,12 @@ def main(argv=None):
     gen.batched_spectral_norm = dis.batched_spectral_norm = True
     augment = None
     if diffaugment:
-        from .augment import DiffAugment
-        augment = DiffAugment(args.image_size, args.batch, policy=diffaugment, seed=args.seed, device=dev)
+        from .augment import AdaptiveDiffAugment, DiffAugment
+        if args.ada_target is not None:
+            augment = AdaptiveDiffAugment(args.image_size, args.batch, policy=diffaugment, seed=args.seed, device=dev, target=args.ada_target,
+                                          interval=args.ada_interval, kimg=args.ada_kimg, initial_p=args.ada_initial_p, p_max=args.ada_p_max)
+        else:
+            augment = DiffAugment(args.image_size, args.batch, policy=diffaugment, seed=args.seed, device=dev)
     step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches, augment=augment)
     pipeline = InputPipeline(DeviceImageStore(args.store, dev), args.image_size, args.batch, seed=args.seed)
     if not args.resume:

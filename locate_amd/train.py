@@ -281,6 +281,15 @@ class TrainStep:
         return out
 
 
+def refuse_adaptive_with_reducer(step):
+    """An adaptive augment steers p from the logits it is shown: under data parallelism every rank would steer its own p from its
+    own shard.  Out of scope, so refused where both can be seen."""
+    if hasattr(getattr(step, "augment", None), "observe") and (getattr(step, "reducer_g", None) is not None
+                                                              or getattr(step, "reducer_d", None) is not None):
+        raise ValueError("an AdaptiveDiffAugment with a data-parallel reducer: each rank would steer its own p from its own shard; "
+                         "use a plain DiffAugment (seed + rank) under data parallelism")
+
+
 class TrainLoop:
     """The reference's batch schedule around the step (main.py:139-172), quirks included:
       * every batch i = 1, 2, ... runs the D-step's forward/backward with `dis.zero_grad()` first - so with
@@ -296,6 +305,7 @@ class TrainLoop:
             raise ValueError("miniter and diters must be >= 1")
         self.step, self.miniter, self.diters = step, int(miniter), int(diters)
         self.i = 0
+        refuse_adaptive_with_reducer(step)
 
     def iteration(self, latent, real, aug):
         """One batch of the loop; returns the D-step record, plus the G-step record when one ran."""
@@ -309,4 +319,6 @@ class TrainLoop:
             if (i // self.miniter) % self.diters == 0:             # :160
                 out.update(step.g_forward_backward(latent))        # :161-169
                 step.g_optimizer()                                 # :171
+        if hasattr(getattr(step, "augment", None), "observe"):
+            step.augment.observe(out["d_true"])                   # adaptive: one launch beside the step; p moves at the next draw()
         return out
