@@ -228,6 +228,14 @@ size_t locate_conv_counter_bytes(void);
  * exactly into three bf16 pieces, six bf16 MFMAs per slice, fp32 accumulation); 1 = bf16 operands (both operands rounded to
  * nearest-even bf16, one MFMA per slice, fp32 accumulation and fp32 storage) - the mixed-precision variant BASELINE.json
  * configs[1] names; tolerance against the fp32 path stated in tests/test_gpu_bf16.py. */
+/* Placement contract of every contraction (locate_conv_*, locate_dwconv_*, locate_groupdot_*): its results depend on the elements
+ * of its own operands only, and it writes the elements of its own outputs only, wherever those lie - an operand or output may be
+ * a channel slice of a wider NCHW tensor (dense [C, H, W] planes, any batch stride >= one sample) that starts on any fp32
+ * element; what lies between the images of a view and around it is neither read into a result (not even against a zero weight)
+ * nor written.  Where a route needs more than 4-byte alignment it either takes another kernel (the pointwise stream, the window
+ * form, the paired-load weight-gradient kernels, the vector bodies of the reductions) or refuses the call with status 1 before
+ * anything is launched (locate_conv_wgrad on its narrow 1x1 route and its 192-row plan: locate_conv_wgrad_operand_align; the
+ * window form: locate_conv_win_ok).  tests/test_gpu_contraction_views.py; the table is DESIGN.md, "Pointer alignment". */
 int locate_conv_fwd(const int* geom, const float* x, int64_t x_bs, const float* panel, const float* scale,
                     int scale_group_batch, int scale_stride, const float* bias, float* y, int64_t y_bs, void* workspace,
                     void* counters, int precision, const void* x_absmax, const void* act_epilogue, void* stream);
@@ -263,6 +271,9 @@ int locate_conv_dgrad(const int* geom, const float* gy, int64_t gy_bs, const flo
  * be 8-byte aligned with an even batch stride - any contiguous tensor is) */
 size_t locate_conv_wgrad_workspace_bytes(const int* geom);
 int locate_conv_wgrad_partials(const int* geom);
+/* bytes that the address and the batch stride of x (which = 0) / gy (which = 1) must be a multiple of for locate_conv_wgrad to
+ * take them at this geometry: 16 (narrow 1x1 route, both), 8 (gy on the 192-row plan) or 4; anything else is refused there */
+int locate_conv_wgrad_operand_align(const int* geom, int which);
 /* deferred_reduce (nullable; host memory, locate_slab_reduce_record_bytes() bytes): the split reduction of this launch is not
  * run but written there; gw / inner_partial are complete after locate_slab_reduce_batch() has run the record (at most
  * locate_slab_reduce_max() records per call; the workspace stays untouched until then).  locate_slab_reduce_record_blocks() == 0:

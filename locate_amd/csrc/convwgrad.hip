@@ -1344,6 +1344,19 @@ LOCATE_API size_t locate_conv_wgrad_workspace_bytes(const int* geom) { return wg
 // number of doubles written to `inner_partial` by locate_conv_wgrad for this geometry
 LOCATE_API int locate_conv_wgrad_partials(const int* geom) { return wgrad_route(make_geom(geom), 0).partials; }
 
+// What locate_conv_wgrad requires of an operand of this geometry (which: 0 = x, 1 = gy): its address and its batch stride are
+// multiples of the returned number of bytes - 16 for both operands of the narrow 1x1 route, 8 for gy on the 192-row plan, 4 (any
+// fp32 tensor) everywhere else.  The route is fixed by the geometry, so an operand that does not meet it is refused at launch; a
+// caller that may hold such a view (a slice of a flat buffer) asks here and copies it first.
+LOCATE_API int locate_conv_wgrad_operand_align(const int* geom, int which) {
+    const ConvGeom g = make_geom(geom);
+    if (geom_check(g, "locate_conv_wgrad_operand_align")) return 4;
+    const WgradRoute r = wgrad_route(g, 0);
+    if (r.kind == WG_POINTWISE) return 16;
+    if (r.kind == WG_TILED && r.bm == 192 && which == 1) return 8;
+    return 4;
+}
+
 // ---- the small weight gradients of a pass in one launch (SkwRec above) ----
 LOCATE_API size_t locate_wgrad_batch_record_bytes(void) { return sizeof(SkwRec); }
 LOCATE_API int locate_wgrad_batch_max(void) { return SKW_MAX; }

@@ -256,7 +256,9 @@ __global__ void __launch_bounds__(256) groupdot_fwd_kernel(const float* __restri
     const float* __restrict__ xp = x + (int64_t)b * x_bs + (int64_t)g * L;
     const float* __restrict__ wp = w + (int64_t)g * L;
     float acc = 0.0f;
-    if ((L & 3) == 0 && (x_bs & 3) == 0) {
+    // 16-byte loads of both rows: g * L and b * x_bs keep the alignment of the two base pointers (a channel slice of a wider tensor
+    // may start on any element)
+    if ((L & 3) == 0 && (x_bs & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15) == 0) {
         const float4* x4 = reinterpret_cast<const float4*>(xp);
         const float4* w4 = reinterpret_cast<const float4*>(wp);
         for (int i = threadIdx.x; i < L / 4; i += 256) {

@@ -1622,6 +1622,17 @@ def _conv_input_grad(gy, x_like, w, owner, spec, geom, garr, sigma, precision=0,
     return gx
 
 
+def _wgrad_operand(L, garr, t, which):
+    """t as locate_conv_wgrad takes it at this geometry (locate_conv_wgrad_operand_align): itself wherever it can - always, for a
+    fresh allocation or a channel slice of one on an even map - or a dense aligned copy."""
+    if (t.data_ptr() | (4 * _bs(t))) & 15 == 0:
+        return t
+    need = L.locate_conv_wgrad_operand_align(garr, which)
+    if t.data_ptr() % need == 0 and (4 * _bs(t)) % need == 0:
+        return t
+    return t.clone(memory_format=torch.contiguous_format)
+
+
 def _raw_weight_grad(spec, geom, garr, xin, gout, gw, w_ref, inv_sigma, sbg, sst, partial, precision=0, amax_in=None, amax_out=None,
                      rt=None, group_dots=0, w_key=None):
     """gw = (sum over the batch of R's input x R's output gradient) / sigma, plus the partial sums of <G, W_bar>.
@@ -1632,6 +1643,10 @@ def _raw_weight_grad(spec, geom, garr, xin, gout, gw, w_ref, inv_sigma, sbg, sst
         CONTRACTION_TAP("wgrad", w_ref if w_ref is not None else w_key, *((xin, gout) if spec.kind == "conv" else (gout, xin)), True)
     L = lib()
     st = _stream()
+    if spec.mode == "dense":
+        # the narrow 1x1 route and the 192-row plan refuse an operand that is only 4-byte aligned (a view that starts inside a
+        # flat buffer): one copy to an aligned dense tensor, as _c16 makes for the unary kernels; every other route takes any view
+        xin, gout = _wgrad_operand(L, garr, xin, 0), _wgrad_operand(L, garr, gout, 1)
     if spec.mode == "dense" and rt is not None and rt.defer_finalisers:
         rec = ctypes.create_string_buffer(L.locate_wgrad_batch_record_bytes())
         if L.locate_wgrad_batch_record(garr, _p(xin), _bs(xin), _p(gout), _bs(gout), _p(gw), _p(w_ref), _p(inv_sigma), sbg, sst,

@@ -480,6 +480,8 @@ def test_conv_window_form_stacked_calls_and_repack(monkeypatch):
         ops._WIN_CACHE.clear()
         buf = torch.zeros(B, M + 8, out_shape[2], out_shape[3], device=dev())
         y = ops._conv_apply(x, w.detach(), w, spec, geom, garr, sigma, bias, out_shape, 0, ops._amax_of(x), buf[:, 8:])
+        assert y.data_ptr() == buf[:, 8:].data_ptr()
+        assert bool((buf[:, :8].view(torch.int32) == 0).all()), "the launch wrote channels of the buffer it does not own"
         return y.clone()
 
     monkeypatch.setattr(ops, "F16_MIN_FLOPS", 0.0)

@@ -21,22 +21,22 @@ copies, add3, the unary kernels' 16-byte and tail bodies - the offset call must 
 
 Needs an MI355X: run with -m gpu."""
 import functools
+import os
 import struct
+import sys
 
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import assert_close
+from conftest import ROOT, assert_close
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "helpers"))
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 8                       # guard words on either side of a view (8 words = 32 bytes: the view's base keeps its alignment)
-SENTINEL = 0x7FC0BEEF           # a quiet NaN with a payload: an over-read shows in the result, an over-write in the guard
-
-
-def dev():
-    return torch.device("cuda:0")
+# the sentinel-guarded buffers (offset_view, offset_out, guards_intact) are shared with tests/test_gpu_contraction_views.py
+from placed_operands import GUARD, SENTINEL, bits, dev, guards_intact, offset_out, offset_view  # noqa: E402,F401
 
 
 def S():
@@ -58,37 +58,6 @@ def status(name, *args):
     st = getattr(L(), name)(*args)
     msg = L().locate_last_error()
     return st, (msg.decode() if msg else "")
-
-
-def offset_view(values, off_elems, align=16):
-    """`values` (float32, any shape) as a contiguous device view that starts off_elems elements past an `align`-byte boundary of a
-    flat buffer filled with SENTINEL, GUARD or more sentinel words in front of it and GUARD behind it."""
-    values = torch.as_tensor(values, dtype=torch.float32)
-    n = values.numel()
-    start = GUARD + off_elems
-    raw = torch.full((start + n + GUARD,), SENTINEL, dtype=torch.int32, device=dev())
-    assert raw.data_ptr() % 32 == 0
-    view = raw.view(torch.float32)[start:start + n].view(values.shape)
-    view.copy_(values)
-    assert view.is_contiguous() and view.data_ptr() % align == (4 * off_elems) % align, (view.data_ptr(), off_elems, align)
-    view._guard = (raw, start, n)
-    return view
-
-
-def offset_out(shape, off_elems, align=16):
-    """an output: every element a NaN until the kernel writes it"""
-    return offset_view(torch.full(tuple(shape), float("nan")), off_elems, align)
-
-
-def guards_intact(*views):
-    for k, v in enumerate(views):
-        raw, start, n = v._guard
-        assert bool((raw[:start] == SENTINEL).all()), "operand %d: the guard words in front of the view were written" % k
-        assert bool((raw[start + n:] == SENTINEL).all()), "operand %d: the guard words behind the view were written" % k
-
-
-def bits(t):
-    return t.detach().contiguous().view(torch.int32).cpu()
 
 
 # ------------------------------------------------------------------------------------------------ softmax
