@@ -767,6 +767,24 @@ int locate_ada_gate(const float* raw_rows, const void* state, float* out_rows, i
 int locate_ada_observe(const float* d_true, int B, int iteration, void* state, void* ring, int capacity, int interval, float target, float step,
                        float p_max, void* stream);
 
+/* ---- LeCam regularisation of the discriminator (csrc/lecam.hip; locate_amd/lecam.py, LeCam; the definition in numpy, which both
+ *      entries equal with ==: tests/helpers/lecam_model.py).  state: a record of 16 32-bit words at a fixed device address - 0 alpha_R,
+ *      the anchor of mean D(real) (fp32), 1 alpha_F, the anchor of mean D(G(z)) (fp32), 2 observations accepted, 3 observations in
+ *      all, 4 observations refused as non-finite, 5 ring rows written, 6 and 7 the last observation's two means (fp32), 8 .. 15 zero.
+ *      d_loss_lecam: the arguments of locate_d_loss plus the record (read only); losses holds 4 floats {d_error, penalty, total, R}.
+ *      Active iff weight != 0 and word 2 >= max(warmup, 1): total = (d_error + penalty) + weight * R with R = mean (t - alpha_F)^2
+ *      + mean (alpha_R - f)^2 (one_sided != 0: both differences through clamp(min=0) first), and the gradients of it.  Inactive:
+ *      losses[0 .. 3) and the three gradients are locate_d_loss's bits and R = 0.
+ *      observe: d_gen is MINUS D(G(z)), the training step's out["d_gen"]; rate = fp32(1 - decay), in [0, 1].  The batch means in
+ *      float64; both finite: the first accepted observation sets the anchors, later ones do alpha += rate * (m - alpha) (three fp32
+ *      operations); otherwise the anchors stay and word 4 counts one.  {iteration, alpha_R, alpha_F, m_R, m_F, accepted, 0, 0} goes
+ *      into ring row (rows written) % capacity (8 words a row).  One block each, no allocation, no host read, no atomics: legal
+ *      under stream capture. ---- */
+int locate_d_loss_lecam(const float* d_true, const float* d_fake, const float* d_aug, int B, float gamma, const void* state, float weight,
+                        int one_sided, int warmup, float* losses, float* g_true, float* g_fake, float* g_aug, void* stream);
+int locate_lecam_observe(const float* d_true, const float* d_gen, int B, int iteration, void* state, void* ring, int capacity, float rate,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -209,6 +209,8 @@ PROTOTYPES = {
     "locate_diffaug_bwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),
     "locate_ada_gate": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
     "locate_ada_observe": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_p]),
+    "locate_d_loss_lecam": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    "locate_lecam_observe": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_f, c_p]),
 }
 
 
@@ -218,7 +220,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 23
+EXPECTED_ABI = 24
 
 
 _lib = None

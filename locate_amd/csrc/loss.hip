@@ -6,40 +6,14 @@
 //            penalty = gamma * (mean t - mean a)^2                   a = D(augmented real)   (not a gradient penalty)
 //   G-step:  g_error = mean( relu(1 - f_i) )
 // clamp(min=0) passes the gradient where its argument is >= 0 (ATen clamp backward mask).
-#include "common.h"
+#include "dloss.h"
 
-// clamp(v, min=0) as ATen computes it: a NaN argument stays NaN (fmaxf would return the 0 and a NaN discriminator output would
-// leave the printed loss finite); its gradient mask (v >= 0) is false there, as ATen's.
-__device__ __forceinline__ float hinge_clamp(float v) { return v < 0.0f ? 0.0f : v; }
-
+// the arithmetic lives in dloss.h, which csrc/lecam.hip shares
 __global__ void __launch_bounds__(256) d_loss_kernel(const float* __restrict__ t, const float* __restrict__ f,
                                                      const float* __restrict__ a, int B, float gamma, float* __restrict__ losses,
                                                      float* __restrict__ gt, float* __restrict__ gf, float* __restrict__ ga) {
     __shared__ double scratch[16];
-    double hs = 0.0, ts = 0.0, as = 0.0;
-    for (int i = threadIdx.x; i < B; i += blockDim.x) {
-        hs += (double)hinge_clamp(1.0f - t[i]) + (double)hinge_clamp(1.0f + f[i]);
-        ts += t[i];
-        as += a[i];
-    }
-    hs = block_sum<double>(hs, scratch);
-    ts = block_sum<double>(ts, scratch);
-    as = block_sum<double>(as, scratch);
-    const float invB = 1.0f / (float)B;
-    const float delta = (float)(ts / B) - (float)(as / B);
-    const float pen_g = 2.0f * gamma * delta * invB;
-    for (int i = threadIdx.x; i < B; i += blockDim.x) {
-        gt[i] = ((1.0f - t[i]) >= 0.0f ? -invB : 0.0f) + pen_g;
-        gf[i] = (1.0f + f[i]) >= 0.0f ? invB : 0.0f;
-        ga[i] = -pen_g;
-    }
-    if (threadIdx.x == 0) {
-        const float d_error = (float)(hs / B);
-        const float pen = gamma * delta * delta;
-        losses[0] = d_error;
-        losses[1] = pen;
-        losses[2] = d_error + pen;
-    }
+    d_loss_plain(t, f, a, B, gamma, losses, gt, gf, ga, scratch);
 }
 
 __global__ void __launch_bounds__(256) g_loss_kernel(const float* __restrict__ f, int B, float* __restrict__ loss,

@@ -10,7 +10,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--manifold 0] [--manifold-k 3] [--spectrum-images 0] [--spectrum-window none]
                              [--msssim-pairs 0] [--modes 0] [--modes-bins 128] [--modes-images 16384]
                              [--diffaugment POLICY] [--ada-target X] [--ada-kimg 500] [--ada-interval 4] [--ada-initial-p 0]
-                             [--ada-p-max 1]
+                             [--ada-p-max 1] [--lecam WEIGHT] [--lecam-decay 0.99] [--lecam-warmup 1000] [--lecam-two-sided]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -86,7 +86,17 @@ Differences from the reference, all additions:
     `OUT/error/ada.json` - {"curve": [{"iteration", "r_t", "p"}, ...], "p", "r_t", "updates", "ups", "downs", "nonfinite"}, the
     curve of the whole run, resumes included - is written after every epoch and when `max_iterations` stops the run.
     `OUT/trainer.torch` and the spill's host state carry p, the open window and both random streams under "augment"; a state saved
-    with `--ada-target` is refused without it and the other way round.  Not under data parallelism."""
+    with `--ada-target` is refused without it and the other way round.  Not under data parallelism;
+  * `--lecam WEIGHT` (off by default): the LeCam regulariser of `locate_amd.lecam` in the D loss - WEIGHT times the mean squared
+    distance of D(real) from the moving average of mean D(G(z)) and of D(G(z)) from that of mean D(real), switched on after
+    `--lecam-warmup` observed iterations (`--lecam-decay`: the averages' decay; `--lecam-two-sided`: the paper's equation in place
+    of the released code's clamped form).  One launch beside the step moves the two averages after every iteration, eager or
+    replayed; their ring is flushed at the progress line, and `OUT/error/lecam.json` - {"curve": [{"iteration", "anchor_real",
+    "anchor_fake", "mean_real", "mean_fake", "accepted"}, ...], "anchor_real", "anchor_fake", "observations", "accepted",
+    "nonfinite", "active"}, the curve of the whole run, resumes included - is written after every epoch and when `max_iterations`
+    stops the run.  `--lecam 0` records the curve and leaves the run bit for bit what it is without.  `OUT/trainer.torch` and the
+    spill's host state carry the averages under "lecam"; a state saved with other settings is refused, a state without one starts
+    the averages at the resumed iteration.  Not under data parallelism."""
 import argparse
 import json
 import os
@@ -278,6 +288,7 @@ class Trainer:
         self.gen, self.dis = step.gen, step.dis
         self.augment = getattr(step, "augment", None)          # a DiffAugment: its rows are drawn before every iteration
         self.adaptive = hasattr(self.augment, "observe")          # an AdaptiveDiffAugment: observed after every iteration
+        self.lecam = getattr(step, "lecam", None)          # a LeCam regulariser: observed after every iteration (TrainLoop does, eagerly)
         self.batch = pipeline.batch
         self.epochs = None if epochs is None else int(epochs)
         self.max_iterations = None if max_iterations is None else int(max_iterations)
@@ -403,6 +414,8 @@ class Trainer:
             state["rollbacks"] = int(self.rollbacks)
         if self.augment is not None:
             state["augment"] = self.augment.state_dict()
+        if self.lecam is not None:
+            state["lecam"] = self.lecam.state_dict()
         path = os.path.join(self.out, STATE_FILE)
         torch.save(state, path + ".tmp")
         os.replace(path + ".tmp", path)
@@ -447,6 +460,8 @@ class Trainer:
             self.rollbacks = int(state.get("rollbacks", 0))
         if self.augment is not None and "augment" in state:          # a run that had none: the parameter stream starts here
             self.augment.load_state_dict(state["augment"])
+        if self.lecam is not None and "lecam" in state:          # a run that had none: the anchors start here
+            self.lecam.load_state_dict(state["lecam"])
         self._last_take = self.iterations         # no committed slot yet: the first take is rollback_every iterations away
         self._last_spill = self.iterations
         return self
@@ -466,6 +481,8 @@ class Trainer:
             state["guard"] = {tag: opt.counters_state() for tag, opt in self._guards()}
         if self.augment is not None:
             state["augment"] = self.augment.state_dict()
+        if self.lecam is not None:
+            state["lecam"] = self.lecam.state_dict()
         return state
 
     def _guards(self):
@@ -568,6 +585,8 @@ class Trainer:
         out = self._runner.replay()
         if self.adaptive:
             self.augment.observe(out["d_true"])          # the replay's logits; the capture's two warm-up iterations are not observed
+        if self.lecam is not None:
+            self.lecam.observe(out["d_true"], out["d_gen"])          # likewise: the anchors move between two replays
         return out
 
     def _progress(self, e, sub, i, first, subepochs, batches, started):
@@ -575,6 +594,8 @@ class Trainer:
         pairs = self.history.flush()          # the one host read of the losses
         if self.adaptive:
             self.augment.flush()          # the ring's new {iteration, r_t, p} rows, here where the loop reads from the device anyway
+        if self.lecam is not None:
+            self.lecam.flush()          # the anchors' curve likewise
         before = self.rollbacks
         self._checks()
         if self.spill is not None and self.rollbacks == before and self.iterations - self._last_spill >= self.spill_every:
@@ -627,6 +648,12 @@ class Trainer:
         across resumes), and the counters of this moment"""
         self.augment.flush()
         return _write_json(os.path.join(self.out, "error", "ada.json"), dict(self.augment.status(), curve=self.augment.curve()))
+
+    def _save_lecam(self):
+        """out/error/lecam.json: the LeCam regulariser's anchors of this moment and their whole curve so far, one row per observed
+        iteration (counted across resumes)"""
+        self.lecam.flush()
+        return _write_json(os.path.join(self.out, "error", "lecam.json"), dict(self.lecam.status(), curve=self.lecam.curve()))
 
     def _measure(self, e):
         """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
@@ -691,6 +718,8 @@ class Trainer:
                         self._checks(before_save=True)
                         if self.adaptive:
                             self.written.append(self._save_ada())
+                        if self.lecam is not None:
+                            self.written.append(self._save_lecam())
                         self.written += self.save_state()
                         return self.iterations
                     followed = self.dynamics is not None and self.dynamics_every and (self.iterations + 1) % self.dynamics_every == 0
@@ -735,6 +764,8 @@ class Trainer:
                 self.written.append(self._save_guards(e + 1))         # raises, before the save below, if a guard is exhausted
             if self.adaptive:
                 self.written.append(self._save_ada())
+            if self.lecam is not None:
+                self.written.append(self._save_lecam())
             if self.swd is not None:
                 self.written.append(self._measure(e))
             if self.neighbours is not None:
@@ -836,6 +867,14 @@ def parser():
     ap.add_argument("--ada-interval", type=int, default=4, metavar="N", help="batches per window of r_t")
     ap.add_argument("--ada-initial-p", type=float, default=0.0, metavar="P")
     ap.add_argument("--ada-p-max", type=float, default=1.0, metavar="P")
+    ap.add_argument("--lecam", type=float, default=None, metavar="WEIGHT",
+                    help="LeCam regularisation of the discriminator: WEIGHT times the mean squared distance of D(real) from the moving "
+                         "average of mean D(G(z)) and of D(G(z)) from that of mean D(real) joins the D loss (the paper: 0.3; 0: only "
+                         "the two averages are recorded); OUT/error/lecam.json holds their curves (default: off)")
+    ap.add_argument("--lecam-decay", type=float, default=0.99, metavar="D", help="decay of the two moving averages")
+    ap.add_argument("--lecam-warmup", type=int, default=1000, metavar="N", help="observed iterations before the regulariser switches on")
+    ap.add_argument("--lecam-two-sided", action="store_true",
+                    help="the paper's equation; default: both distances clamped at 0 before squaring, the released code's form")
     return ap
 
 
@@ -902,6 +941,13 @@ def main(argv=None):
             ap.error("--ada-p-max must be in (0, 1]")
         if not 0.0 <= args.ada_initial_p <= args.ada_p_max:
             ap.error("--ada-initial-p must be in [0, --ada-p-max]")
+    if args.lecam is not None:
+        if not abs(args.lecam) < float("inf"):
+            ap.error("--lecam must be a finite number")
+        if not 0.0 <= args.lecam_decay <= 1.0:
+            ap.error("--lecam-decay must be in [0, 1]")
+        if not 0 <= args.lecam_warmup < 1 << 31:
+            ap.error("--lecam-warmup must be in 0 .. 2^31 - 1")
     guarded_step = args.clip_grad_norm is not None or args.no_skip_nonfinite
     if args.rollback_every > 0 and not (args.stats_every > 0 or guarded_step):
         ap.error("--rollback-every needs --stats-every or a guarded optimizer (--clip-grad-norm / --no-skip-nonfinite): "
@@ -930,7 +976,12 @@ def main(argv=None):
                                           interval=args.ada_interval, kimg=args.ada_kimg, initial_p=args.ada_initial_p, p_max=args.ada_p_max)
         else:
             augment = DiffAugment(args.image_size, args.batch, policy=diffaugment, seed=args.seed, device=dev)
-    step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches, augment=augment)
+    lecam = None
+    if args.lecam is not None:
+        from .lecam import LeCam
+        lecam = LeCam(args.batch, weight=args.lecam, decay=args.lecam_decay, warmup=args.lecam_warmup, one_sided=not args.lecam_two_sided,
+                      device=dev)
+    step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches, augment=augment, lecam=lecam)
     pipeline = InputPipeline(DeviceImageStore(args.store, dev), args.image_size, args.batch, seed=args.seed)
     if not args.resume:
         os.makedirs(args.out, exist_ok=True)

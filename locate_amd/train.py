@@ -44,8 +44,13 @@ def g_loss(d_fake):
 
 class TrainStep:
     def __init__(self, gen, dis, gen_opt, dis_opt, penalty_gamma=100.0, minibatches=1, reducer_g=None, reducer_d=None,
-                 concurrent_d=False, stacked_d=None, overlap_wgrad=False, d_cut=None, augment=None):
+                 concurrent_d=False, stacked_d=None, overlap_wgrad=False, d_cut=None, augment=None, lecam=None):
         self.gen, self.dis, self.gen_opt, self.dis_opt = gen, dis, gen_opt, dis_opt
+        # lecam: a locate_amd.lecam.LeCam.  The D-step's loss launch becomes its d_loss - the same launch with the LeCam regulariser,
+        # which reads its anchors from a device record - and the step's record gains "lecam", the unweighted regulariser.  The caller
+        # observes after the iteration (lecam.observe(out["d_true"], out["d_gen"]); TrainLoop.iteration and Trainer do).  None: every
+        # launch and key is what it was.
+        self.lecam = lecam
         # augment: a locate_amd.augment.DiffAugment.  Every batch the discriminator sees - the D-step's three thirds, the G-step's
         # fake - passes through its random transform T first, and the G-step's gradient flows back through T into the generator.
         # The caller draws the iteration's rows (augment.draw(); TrainLoop.iteration and Trainer do).  The returned images stay
@@ -177,9 +182,11 @@ class TrainStep:
                 seen = self.augment.d_batch(seen)      # T of the whole [3B] batch in one launch; nothing here needs a gradient
             d_all = dis(seen, stacked=3, cut_after=cut)   # :149, :150, grad_penalty.py:2
             d_true, d_fake, d_aug = d_all[:B], d_all[B:2 * B], d_all[2 * B:]
-            losses, g_t, _, _ = d_loss(d_true, d_fake, d_aug, self.penalty_gamma)
+            losses, g_t, _, _ = self._d_loss(d_true, d_fake, d_aug)
             out = {"d_error": losses[0], "penalty": losses[1], "d_true": d_true.detach().view(-1),
                    "d_gen": -d_fake.detach().view(-1), "generated": generated}
+            if self.lecam is not None:
+                out["lecam"] = losses[3]
             if self.reducer_d is not None:
                 self.reducer_d.begin()
             self._backward([d_all], [g_t._base.view_as(d_all)])                 # :156
@@ -202,14 +209,23 @@ class TrainStep:
             d_true = dis(self._seen(real, 0))      # :149
             d_fake = dis(self._seen(generated, 1)) # :150 (the reference negates it; the loss kernel takes it raw)
             d_aug = dis(self._seen(aug, 2))        # grad_penalty.py:2
-        losses, g_t, g_f, g_a = d_loss(d_true, d_fake, d_aug, self.penalty_gamma)
+        losses, g_t, g_f, g_a = self._d_loss(d_true, d_fake, d_aug)
         if self.reducer_d is not None:
             self.reducer_d.begin()
         self._backward([d_true, d_fake, d_aug], [g_t.view_as(d_true), g_f.view_as(d_fake), g_a.view_as(d_aug)])  # :156
         if self.reducer_d is not None:
             self.reducer_d.finish()
-        return {"d_error": losses[0], "penalty": losses[1], "d_true": d_true.detach().view(-1),
-                "d_gen": -d_fake.detach().view(-1), "generated": generated}
+        out = {"d_error": losses[0], "penalty": losses[1], "d_true": d_true.detach().view(-1),
+               "d_gen": -d_fake.detach().view(-1), "generated": generated}
+        if self.lecam is not None:
+            out["lecam"] = losses[3]
+        return out
+
+    def _d_loss(self, d_true, d_fake, d_aug):
+        """the D-step's one loss launch: plain, or the LeCam regulariser's"""
+        if self.lecam is None:
+            return d_loss(d_true, d_fake, d_aug, self.penalty_gamma)
+        return self.lecam.d_loss(d_true, d_fake, d_aug, self.penalty_gamma)
 
     @staticmethod
     def _repack(net):
@@ -290,6 +306,15 @@ def refuse_adaptive_with_reducer(step):
                          "use a plain DiffAugment (seed + rank) under data parallelism")
 
 
+def refuse_lecam_with_reducer(step):
+    """A LeCam regulariser keeps anchors of the logits it is shown: under data parallelism every rank would keep anchors of its own
+    shard, and regularise towards them.  Out of scope, so refused where both can be seen."""
+    if getattr(step, "lecam", None) is not None and (getattr(step, "reducer_g", None) is not None
+                                                     or getattr(step, "reducer_d", None) is not None):
+        raise ValueError("a LeCam regulariser with a data-parallel reducer: each rank would keep anchors of its own shard; "
+                         "run without lecam under data parallelism")
+
+
 class TrainLoop:
     """The reference's batch schedule around the step (main.py:139-172), quirks included:
       * every batch i = 1, 2, ... runs the D-step's forward/backward with `dis.zero_grad()` first - so with
@@ -306,6 +331,7 @@ class TrainLoop:
         self.step, self.miniter, self.diters = step, int(miniter), int(diters)
         self.i = 0
         refuse_adaptive_with_reducer(step)
+        refuse_lecam_with_reducer(step)
 
     def iteration(self, latent, real, aug):
         """One batch of the loop; returns the D-step record, plus the G-step record when one ran."""
@@ -321,4 +347,6 @@ class TrainLoop:
                 step.g_optimizer()                                 # :171
         if hasattr(getattr(step, "augment", None), "observe"):
             step.augment.observe(out["d_true"])                   # adaptive: one launch beside the step; p moves at the next draw()
+        if getattr(step, "lecam", None) is not None:
+            step.lecam.observe(out["d_true"], out["d_gen"])       # the anchors move after the iteration that read them
         return out
