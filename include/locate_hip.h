@@ -785,6 +785,20 @@ int locate_d_loss_lecam(const float* d_true, const float* d_fake, const float* d
 int locate_lecam_observe(const float* d_true, const float* d_gen, int B, int iteration, void* state, void* ring, int capacity, float rate,
                          void* stream);
 
+/* ---- Top-k training of the generator (csrc/topk.hip; locate_amd/topk.py, TopK; the definition in numpy, which the entry equals
+ *      with ==: tests/helpers/topk_model.py).  locate_g_loss's launch in which only the k logits that stand first contribute to
+ *      losses[0] and to g_fake.  j stands before i iff f_j is a NaN and f_i is not, or both are and j < i, or neither is and f_j > f_i,
+ *      or neither is, f_j == f_i (-0 == +0) and j < i; an element is kept iff fewer than k_used stand before it.  record: 16 32-bit
+ *      words at a fixed device address - 0 k (int32, read only; outside 1 .. B: k_used = B), 1 launches, 2 launches whose logits held
+ *      a NaN or an Inf, 3 k_used, 4 kept elements with (1 - f) >= 0, 5 the fp32 bits of the kept element of rank k_used - 1, 6
+ *      (float)(sum f / B), 7 (float)(sum_kept f / k_used), 8 .. 15 zero.  ring: `capacity` rows of 8 words {launch ordinal (1-based),
+ *      k_used, active, threshold, mean_all, mean_kept, non-finite 0 / 1, 0}, row (ordinal - 1) % capacity.  losses: 2 floats
+ *      {loss_topk = (float)(sum_kept relu(1 - f) / k_used), loss_all = locate_g_loss's bits}; g_fake[i] = -(1 / k_used) where i is
+ *      kept and (1 - f_i) >= 0, else +0.  1 <= B <= 4096.  form: 0 chooses the selection by B, 1 counts ranks, 2 sorts; the same bits.
+ *      One block, no allocation, no host read, no atomics: legal under stream capture. ---- */
+int locate_g_loss_topk(const float* d_fake, int B, void* record, void* ring, int capacity, int form, float* losses, float* g_fake,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ from .modes import BinnedModes, centroids, group_sums, kmeans_codes, ndb_statist
 from .average import AveragedGenerator, average_weight  # noqa: F401
 from .augment import AdaptiveDiffAugment, DiffAugment, diff_augment, diff_augment_backward, draw_parameters  # noqa: F401
 from .lecam import LeCam  # noqa: F401
+from .topk import TopK, topk_k  # noqa: F401
 from .stats import NonFiniteError, RunStatistics, tensor_statistics  # noqa: F401
 from .dynamics import RunDynamics, tensor_deltas  # noqa: F401
 from .formats import FormatAudit, format_errors  # noqa: F401

@@ -211,6 +211,7 @@ PROTOTYPES = {
     "locate_ada_observe": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_f, c_f, c_f, c_p]),
     "locate_d_loss_lecam": (c_i, [c_p, c_p, c_p, c_i, c_f, c_p, c_f, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     "locate_lecam_observe": (c_i, [c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_f, c_p]),
+    "locate_g_loss_topk": (c_i, [c_p, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p]),
 }
 
 
@@ -220,7 +221,7 @@ class LocateError(RuntimeError):
 
 # bumped together with locate_abi_version() in csrc/runtime.hip whenever a prototype above changes: a stale .so that still
 # exports every NAME would otherwise be called with shifted arguments
-EXPECTED_ABI = 24
+EXPECTED_ABI = 25
 
 
 _lib = None

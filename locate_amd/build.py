@@ -17,7 +17,7 @@ LIB = os.path.join(CSRC, "liblocate_hip.so")
 LIB_DBG = os.path.join(CSRC, "liblocate_hip_dbg.so")
 DBG_SOURCES = ["conv.hip", "convwgrad.hip", "convwin.hip", "snapshot.hip"]
 SOURCES = ["runtime.hip", "elementwise.hip", "norm.hip", "softmax.hip", "resample.hip", "spectral.hip", "conv.hip", "convpack.hip", "convwgrad.hip", "convwin.hip", "convfp8.hip",
-           "grouped.hip", "nadam.hip", "loss.hip", "finalise.hip", "parallel.hip", "input.hip", "grid.hip", "swd.hip", "average.hip", "stats.hip", "guard.hip", "snapshot.hip", "digest.hip", "dynamics.hip", "neighbours.hip", "formats.hip", "spectrum.hip", "msssim.hip", "modes.hip", "diffaug.hip", "ada.hip", "lecam.hip"]
+           "grouped.hip", "nadam.hip", "loss.hip", "finalise.hip", "parallel.hip", "input.hip", "grid.hip", "swd.hip", "average.hip", "stats.hip", "guard.hip", "snapshot.hip", "digest.hip", "dynamics.hip", "neighbours.hip", "formats.hip", "spectrum.hip", "msssim.hip", "modes.hip", "diffaug.hip", "ada.hip", "lecam.hip", "topk.hip"]
 ARCH = "gfx950"
 
 

@@ -120,6 +120,29 @@ __device__ __forceinline__ T block_sum(T v, T* scratch) {
     for (int i = 0; i < nw; ++i) t += scratch[i];
     return t;
 }
+// block_sum() of N float64 values behind ONE pair of barriers, for a block of 64 * WAVES threads: per value the same xor butterfly
+// and the same in-order sum of the wave results, so every value has block_sum's bits.  scratch: N * WAVES doubles.
+template <int N, int WAVES>
+__device__ __forceinline__ void block_sums(double (&v)[N], double* scratch) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) scratch[k * WAVES + wid] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        double total = 0;
+        for (int i = 0; i < WAVES; ++i) total += scratch[k * WAVES + i];
+        v[k] = total;
+    }
+}
 __device__ __forceinline__ float block_max(float v, float* scratch) {
     v = wave_max(v);
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;

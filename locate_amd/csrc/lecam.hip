@@ -56,29 +56,10 @@ __device__ __forceinline__ float lecam_total(float d_error, float pen, float wei
     return plain + wr;
 }
 
-// block_sum() (common.h) of N values behind ONE pair of barriers: per value the same xor butterfly and the same in-order sum of the
-// wave results, so every value has block_sum's bits.  scratch: N * (LECAM_THREADS / 64) doubles.
+// the sums of one pass behind ONE pair of barriers (common.h, block_sums; csrc/topk.hip shares it): every sum has block_sum's bits
 template <int N>
 __device__ __forceinline__ void lecam_block_sums(double (&v)[N], double* scratch) {
-    constexpr int WAVES = LECAM_THREADS / 64;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-    }
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) scratch[k * WAVES + wid] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double total = 0;
-        for (int i = 0; i < WAVES; ++i) total += scratch[k * WAVES + i];
-        v[k] = total;
-    }
+    block_sums<N, LECAM_THREADS / 64>(v, scratch);
 }
 
 __global__ void __launch_bounds__(LECAM_THREADS) d_loss_lecam_kernel(const float* __restrict__ t, const float* __restrict__ f,

@@ -7,8 +7,9 @@
 //   G-step:  g_error = mean( relu(1 - f_i) )
 // clamp(min=0) passes the gradient where its argument is >= 0 (ATen clamp backward mask).
 #include "dloss.h"
+#include "gloss.h"
 
-// the arithmetic lives in dloss.h, which csrc/lecam.hip shares
+// the arithmetic lives in dloss.h, which csrc/lecam.hip shares, and in gloss.h, which csrc/topk.hip shares
 __global__ void __launch_bounds__(256) d_loss_kernel(const float* __restrict__ t, const float* __restrict__ f,
                                                      const float* __restrict__ a, int B, float gamma, float* __restrict__ losses,
                                                      float* __restrict__ gt, float* __restrict__ gf, float* __restrict__ ga) {
@@ -22,11 +23,11 @@ __global__ void __launch_bounds__(256) g_loss_kernel(const float* __restrict__ f
     double hs = 0.0;
     const float invB = 1.0f / (float)B;
     for (int i = threadIdx.x; i < B; i += blockDim.x) {
-        hs += (double)hinge_clamp(1.0f - f[i]);
-        gf[i] = (1.0f - f[i]) >= 0.0f ? -invB : 0.0f;
+        hs += g_hinge_term(f[i]);
+        gf[i] = g_hinge_grad(f[i], invB);
     }
     hs = block_sum<double>(hs, scratch);
-    if (threadIdx.x == 0) loss[0] = (float)(hs / B);
+    if (threadIdx.x == 0) loss[0] = g_hinge_mean(hs, B);
 }
 
 // losses: 3 floats {d_error, penalty, d_error + penalty};  g_*: [B] gradients of the total w.r.t. each D output

@@ -11,6 +11,7 @@ end of every pass, the loss curves and a checkpoint after every epoch.  Host glu
                              [--msssim-pairs 0] [--modes 0] [--modes-bins 128] [--modes-images 16384]
                              [--diffaugment POLICY] [--ada-target X] [--ada-kimg 500] [--ada-interval 4] [--ada-initial-p 0]
                              [--ada-p-max 1] [--lecam WEIGHT] [--lecam-decay 0.99] [--lecam-warmup 1000] [--lecam-two-sided]
+                             [--topk-floor F] [--topk-gamma 0.99] [--topk-every N]
 
 Differences from the reference, all additions:
   * `--resume` / `Trainer.resume()`: the reference cannot continue a run.  Here `OUT/trainer.torch` (epoch, sub-pass, position,
@@ -96,7 +97,16 @@ Differences from the reference, all additions:
     "nonfinite", "active"}, the curve of the whole run, resumes included - is written after every epoch and when `max_iterations`
     stops the run.  `--lecam 0` records the curve and leaves the run bit for bit what it is without.  `OUT/trainer.torch` and the
     spill's host state carry the averages under "lecam"; a state saved with other settings is refused, a state without one starts
-    the averages at the resumed iteration.  Not under data parallelism."""
+    the averages at the resumed iteration.  Not under data parallelism;
+  * `--topk-floor F` (off by default): top-k training of the generator, `locate_amd.topk` - the G-step's loss and gradient run over
+    the k fakes with the highest D(G(z)) only, k = the batch size times `--topk-gamma` to the power of the periods done, never below
+    F times the batch size; a period is `--topk-every` iterations (default: one pass over the image store).  k is moved before the
+    iteration, eager or replayed; the selection's ring is flushed at the progress line, and `OUT/error/topk.json` - {"curve":
+    [{"launch", "k", "active", "threshold", "mean_all", "mean_kept", "nonfinite"}, ...], "k", "k_used", "launches", "nonfinite",
+    "active", "threshold", "mean_all", "mean_kept"}, one row per launch of the G-step's loss over the whole run, resumes included -
+    is written after every epoch and when `max_iterations` stops the run.  The printed g_error is the loss over the kept k.
+    `--topk-gamma 1` leaves the run bit for bit what it is without.  `OUT/trainer.torch` and the spill's host state carry the record
+    and the curve under "topk"; a state saved with other settings is refused; a rollback does not rewind it."""
 import argparse
 import json
 import os
@@ -289,6 +299,7 @@ class Trainer:
         self.augment = getattr(step, "augment", None)          # a DiffAugment: its rows are drawn before every iteration
         self.adaptive = hasattr(self.augment, "observe")          # an AdaptiveDiffAugment: observed after every iteration
         self.lecam = getattr(step, "lecam", None)          # a LeCam regulariser: observed after every iteration (TrainLoop does, eagerly)
+        self.topk = getattr(step, "topk", None)          # a TopK selection: k is moved before every iteration (TrainLoop does, eagerly)
         self.batch = pipeline.batch
         self.epochs = None if epochs is None else int(epochs)
         self.max_iterations = None if max_iterations is None else int(max_iterations)
@@ -416,6 +427,8 @@ class Trainer:
             state["augment"] = self.augment.state_dict()
         if self.lecam is not None:
             state["lecam"] = self.lecam.state_dict()
+        if self.topk is not None:
+            state["topk"] = self.topk.state_dict()
         path = os.path.join(self.out, STATE_FILE)
         torch.save(state, path + ".tmp")
         os.replace(path + ".tmp", path)
@@ -462,6 +475,8 @@ class Trainer:
             self.augment.load_state_dict(state["augment"])
         if self.lecam is not None and "lecam" in state:          # a run that had none: the anchors start here
             self.lecam.load_state_dict(state["lecam"])
+        if self.topk is not None and "topk" in state:          # a run that had none: the curve starts here, k follows the iteration count
+            self.topk.load_state_dict(state["topk"])
         self._last_take = self.iterations         # no committed slot yet: the first take is rollback_every iterations away
         self._last_spill = self.iterations
         return self
@@ -483,6 +498,8 @@ class Trainer:
             state["augment"] = self.augment.state_dict()
         if self.lecam is not None:
             state["lecam"] = self.lecam.state_dict()
+        if self.topk is not None:
+            state["topk"] = self.topk.state_dict()
         return state
 
     def _guards(self):
@@ -570,9 +587,12 @@ class Trainer:
         if not self.graphed:
             latent = torch.randn(latent_shape, device=self.device, generator=self._latent_gen)          # main.py:142
             real, aug = self.pipeline.next_batch()
-            return self.loop.iteration(latent, real, aug)          # draws the augmentation's rows itself
+            self.loop.iterations = self.iterations          # what the top-k schedule counts: i restarts with every sub-pass
+            return self.loop.iteration(latent, real, aug)          # draws the augmentation's rows and moves k itself
         if self.augment is not None:
             self.augment.draw()          # the graphs read the rows at a fixed address: whatever was uploaded last
+        if self.topk is not None:
+            self.topk.advance(self.iterations)          # likewise word 0 of its record: the capture's warm-up runs with this k too
         if self._runner is None:
             from .graph import GraphedTrainStep
             latent = torch.randn(latent_shape, device=self.device, generator=self._latent_gen)
@@ -596,6 +616,8 @@ class Trainer:
             self.augment.flush()          # the ring's new {iteration, r_t, p} rows, here where the loop reads from the device anyway
         if self.lecam is not None:
             self.lecam.flush()          # the anchors' curve likewise
+        if self.topk is not None:
+            self.topk.flush()          # and the selection's rows
         before = self.rollbacks
         self._checks()
         if self.spill is not None and self.rollbacks == before and self.iterations - self._last_spill >= self.spill_every:
@@ -654,6 +676,12 @@ class Trainer:
         iteration (counted across resumes)"""
         self.lecam.flush()
         return _write_json(os.path.join(self.out, "error", "lecam.json"), dict(self.lecam.status(), curve=self.lecam.curve()))
+
+    def _save_topk(self):
+        """out/error/topk.json: the top-k selection's record of this moment and its whole curve so far, one row per launch of the
+        G-step's loss (counted across resumes)"""
+        self.topk.flush()
+        return _write_json(os.path.join(self.out, "error", "topk.json"), dict(self.topk.status(), curve=self.topk.curve()))
 
     def _measure(self, e):
         """One record of the sliced Wasserstein distance into out/error/swd.json (written to a .tmp and renamed)."""
@@ -720,6 +748,8 @@ class Trainer:
                             self.written.append(self._save_ada())
                         if self.lecam is not None:
                             self.written.append(self._save_lecam())
+                        if self.topk is not None:
+                            self.written.append(self._save_topk())
                         self.written += self.save_state()
                         return self.iterations
                     followed = self.dynamics is not None and self.dynamics_every and (self.iterations + 1) % self.dynamics_every == 0
@@ -766,6 +796,8 @@ class Trainer:
                 self.written.append(self._save_ada())
             if self.lecam is not None:
                 self.written.append(self._save_lecam())
+            if self.topk is not None:
+                self.written.append(self._save_topk())
             if self.swd is not None:
                 self.written.append(self._measure(e))
             if self.neighbours is not None:
@@ -875,6 +907,13 @@ def parser():
     ap.add_argument("--lecam-warmup", type=int, default=1000, metavar="N", help="observed iterations before the regulariser switches on")
     ap.add_argument("--lecam-two-sided", action="store_true",
                     help="the paper's equation; default: both distances clamped at 0 before squaring, the released code's form")
+    ap.add_argument("--topk-floor", type=float, default=None, metavar="F",
+                    help="top-k training of the generator: the G-step's loss runs over the k fakes with the highest D(G(z)), k annealed "
+                         "from the batch size down to F times the batch size; OUT/error/topk.json holds the selection's curve "
+                         "(default: off)")
+    ap.add_argument("--topk-gamma", type=float, default=0.99, metavar="G", help="k's decay per period")
+    ap.add_argument("--topk-every", type=int, default=None, metavar="N",
+                    help="iterations per period (default: one pass over the image store)")
     return ap
 
 
@@ -948,6 +987,17 @@ def main(argv=None):
             ap.error("--lecam-decay must be in [0, 1]")
         if not 0 <= args.lecam_warmup < 1 << 31:
             ap.error("--lecam-warmup must be in 0 .. 2^31 - 1")
+    if args.topk_floor is not None:
+        if not 0.0 <= args.topk_floor <= 1.0:
+            ap.error("--topk-floor must be in [0, 1]")
+        if not 0.0 < args.topk_gamma <= 1.0:
+            ap.error("--topk-gamma must be in (0, 1]")
+        if args.topk_every is not None and not 1 <= args.topk_every < 1 << 31:
+            ap.error("--topk-every must be in 1 .. 2^31 - 1")
+        if not 1 <= args.batch <= 4096:
+            ap.error("--topk-floor needs a batch of at most 4096")
+    elif args.topk_every is not None or args.topk_gamma != 0.99:
+        ap.error("--topk-gamma and --topk-every need --topk-floor")
     guarded_step = args.clip_grad_norm is not None or args.no_skip_nonfinite
     if args.rollback_every > 0 and not (args.stats_every > 0 or guarded_step):
         ap.error("--rollback-every needs --stats-every or a guarded optimizer (--clip-grad-norm / --no-skip-nonfinite): "
@@ -981,8 +1031,13 @@ def main(argv=None):
         from .lecam import LeCam
         lecam = LeCam(args.batch, weight=args.lecam, decay=args.lecam_decay, warmup=args.lecam_warmup, one_sided=not args.lecam_two_sided,
                       device=dev)
-    step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches, augment=augment, lecam=lecam)
     pipeline = InputPipeline(DeviceImageStore(args.store, dev), args.image_size, args.batch, seed=args.seed)
+    topk = None
+    if args.topk_floor is not None:
+        from .topk import TopK
+        topk = TopK(args.batch, gamma=args.topk_gamma, floor=args.topk_floor, every=args.topk_every or max(1, pipeline.batches_per_epoch),
+                    device=dev)
+    step = TrainStep(gen, dis, gen_opt, dis_opt, minibatches=args.minibatches, augment=augment, lecam=lecam, topk=topk)
     if not args.resume:
         os.makedirs(args.out, exist_ok=True)
 

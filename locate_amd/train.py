@@ -44,8 +44,14 @@ def g_loss(d_fake):
 
 class TrainStep:
     def __init__(self, gen, dis, gen_opt, dis_opt, penalty_gamma=100.0, minibatches=1, reducer_g=None, reducer_d=None,
-                 concurrent_d=False, stacked_d=None, overlap_wgrad=False, d_cut=None, augment=None, lecam=None):
+                 concurrent_d=False, stacked_d=None, overlap_wgrad=False, d_cut=None, augment=None, lecam=None, topk=None):
         self.gen, self.dis, self.gen_opt, self.dis_opt = gen, dis, gen_opt, dis_opt
+        # topk: a locate_amd.topk.TopK.  The G-step's loss launch becomes its g_loss - the same launch over the k logits that stand
+        # first, k read from a device record - so "g_error" is the loss over those k, and the step's record gains "g_error_all", the
+        # plain loss over the whole batch, and "g_logits", the raw D(G(z)) of that pass.  The caller moves k between iterations
+        # (topk.advance(iterations done); TrainLoop.iteration and Trainer do).  Legal beside a reducer: each rank selects within its
+        # shard, and k is the same function of the iteration on every rank.  None: every launch and key is what it was.
+        self.topk = topk
         # lecam: a locate_amd.lecam.LeCam.  The D-step's loss launch becomes its d_loss - the same launch with the LeCam regulariser,
         # which reads its anchors from a device record - and the step's record gains "lecam", the unweighted regulariser.  The caller
         # observes after the iteration (lecam.observe(out["d_true"], out["d_gen"]); TrainLoop.iteration and Trainer do).  None: every
@@ -244,7 +250,7 @@ class TrainStep:
                 gen.zero_grad()
                 fake = gen(latent)
                 d_out = dis(fake if self.augment is None else self.augment.g_batch(fake))
-                loss, g = g_loss(d_out)
+                loss, g = self._g_loss(d_out)
                 if self.reducer_g is not None:
                     self.reducer_g.begin()
                 self._backward([d_out], [g.view_as(d_out)])
@@ -252,7 +258,7 @@ class TrainStep:
                     self.reducer_g.finish()
         finally:
             dis.requires_grad_(True)               # :172 (u, v included; the reference does it after GEN_OPTIM.step())
-        return {"g_error": loss[0], "fake": fake.detach()}
+        return self._g_record(loss, d_out, fake)
 
     # the G-step in two phases (minibatches == 1): its generator pass depends on nothing the D-step changes, so graph.py
     # replays it on a second stream while the D-step's discriminator work is still running
@@ -265,7 +271,7 @@ class TrainStep:
         dis.requires_grad_(False)                  # main.py:161
         try:
             d_out = dis(fake if self.augment is None else self.augment.g_batch(fake))
-            loss, g = g_loss(d_out)
+            loss, g = self._g_loss(d_out)
             if self.reducer_g is not None:
                 self.reducer_g.begin()
             self._backward([d_out], [g.view_as(d_out)])   # :169
@@ -273,7 +279,20 @@ class TrainStep:
                 self.reducer_g.finish()
         finally:
             dis.requires_grad_(True)               # :172
-        return {"g_error": loss[0], "fake": fake.detach()}
+        return self._g_record(loss, d_out, fake)
+
+    def _g_loss(self, d_out):
+        """the G-step's one loss launch: plain (loss[1]), or the top-k selection's (losses[2] = {over the kept k, over the batch})"""
+        if self.topk is None:
+            return g_loss(d_out)
+        return self.topk.g_loss(d_out)
+
+    def _g_record(self, loss, d_out, fake):
+        out = {"g_error": loss[0], "fake": fake.detach()}
+        if self.topk is not None:
+            out["g_error_all"] = loss[1]
+            out["g_logits"] = d_out.detach().view(-1)
+        return out
 
     def g_optimizer(self):
         from . import ops
@@ -330,6 +349,7 @@ class TrainLoop:
             raise ValueError("miniter and diters must be >= 1")
         self.step, self.miniter, self.diters = step, int(miniter), int(diters)
         self.i = 0
+        self.iterations = 0          # iterations done in all (i restarts with every sub-pass of a Trainer, which sets this on resume)
         refuse_adaptive_with_reducer(step)
         refuse_lecam_with_reducer(step)
 
@@ -339,6 +359,8 @@ class TrainLoop:
         i, step = self.i, self.step
         if getattr(step, "augment", None) is not None:
             step.augment.draw()                                    # this iteration's rows, the D-step's and the G-step's
+        if getattr(step, "topk", None) is not None:
+            step.topk.advance(self.iterations)                     # the schedule's k: one small copy, and only when k moves
         out = step.d_forward_backward(latent, real, aug)          # main.py:146-156
         if i % self.miniter == 0:                                  # :158
             step.d_optimizer()                                     # :159
@@ -349,4 +371,5 @@ class TrainLoop:
             step.augment.observe(out["d_true"])                   # adaptive: one launch beside the step; p moves at the next draw()
         if getattr(step, "lecam", None) is not None:
             step.lecam.observe(out["d_true"], out["d_gen"])       # the anchors move after the iteration that read them
+        self.iterations += 1
         return out
